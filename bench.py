@@ -11,7 +11,12 @@ FASTQ record scan + descriptor emission, plus the all-gather of per-chunk record
 N > 1.  Decompressed output streams through a reused device buffer (out_capacity), as a
 consumer enumerating records would.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--workload 50gb|1m]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--workload 50gb|1m] [--full] [--dump-outputs DIR]
+  A plain run sets up, warms up, times the K steps and prints the result line.  --full adds the
+  side measurements, each reported under its own key and never as value: the CPU baseline, the
+  end-to-end ingest and enumerator legs, the per-chunk Decompress legs (and, with --paired, the
+  pair chunks' byte comparison and the decode + check only timing).  --dump-outputs DIR writes what
+  the last timed step computed as DIR/<name>.npy (dump_shard).
   N > 1: one process per GPU, backend nccl = RCCL.  Under torch.distributed.run (WORLD_SIZE set)
   this process is one rank; started directly with --gpus N > 1 it launches the N ranks itself
   (torch.distributed.run as a child, before anything touches the GPU) and exits with its code.
@@ -821,19 +826,26 @@ def paired_run(args, dev, world=1, rank=0, xdev=None, backend="nccl"):
                 "ms_per_step": statistics.median(emit_ms[-args.steps:]) if emit_ms else None,
                 "last_step_ms": {k: round(est[k], 2) for k in ("rerun_ms", "pack_ms", "exchange_ms", "emit_ms")},
                 "batches_rerun_per_step": est["reruns"],
-                "verified": verify_pair_chunks(pairs, tfs, K, shards, comm, world, rank),
+                "verified": verify_pair_chunks(pairs, tfs, K, shards, comm, world, rank) if args.full else None,
                 "note": "every pair chunk of this rank packed on the device per step (records back to back + "
                         "descriptors per half, ppg_pairs_emit_*), inside the timed step; one rank: the emission "
                         "drives the shards' own run (ppg_pairs_emit_run: each output batch decoded once, its "
                         "halves packed while resident; ms_per_step = decode + packing, rerun_ms = the batches' "
                         "runs), the pair check after it; N ranks: decode, check, then the records moved to "
                         "their pair chunk's owner"}
-    # the previous round's line (decode + check, no emission) for comparison, timed after the main loop
-    t1 = time.perf_counter()
-    for _ in range(args.steps):
-        step(emit=False)
-    torch.cuda.synchronize()
-    check_only = (time.perf_counter() - t1) / args.steps
+    if args.dump_outputs:
+        sfx = f"_rank{rank}" if world > 1 else ""
+        for f, sh in enumerate(shards):
+            dump_shard(args.dump_outputs, sh, f"_r{f + 1}{sfx}", DUMP_BUDGET // (2 * world))
+        np.save(os.path.join(args.dump_outputs, f"pairs{sfx}.npy"), np.array([npairs], np.float64))
+    check_only = None
+    if args.full:
+        # the previous round's line (decode + check, no emission) for comparison, timed after the main loop
+        t1 = time.perf_counter()
+        for _ in range(args.steps):
+            step(emit=False)
+        torch.cuda.synchronize()
+        check_only = (time.perf_counter() - t1) / args.steps
     return {
         "metric": f"paired-end record pairs/sec (R1+R2 DecompressAll + pair check + record-aligned pair chunks), "
                   f"{world} MI355X",
@@ -859,9 +871,10 @@ def paired_run(args, dev, world=1, rank=0, xdev=None, backend="nccl"):
         "decompressed_MBps": text * args.steps / elapsed / 1e6,
         "setup_s": {"input": round(args.input_seconds, 2), "shards": round(setup_s, 2)},
         "emission": emission,
-        "without_emission": {"pairs_per_s": npairs / check_only if world == 1 else None,
-                             "ms_per_step": check_only * 1e3,
-                             "note": "decode + pair check only (the r04 line), rank 0's own clock"},
+        **({"without_emission": {"pairs_per_s": npairs / check_only if world == 1 else None,
+                                 "ms_per_step": check_only * 1e3,
+                                 "note": "decode + pair check only (the r04 line), rank 0's own clock"}}
+           if args.full else {}),
     }
 
 
@@ -905,6 +918,42 @@ def tiled_records(tf, lo, hi):
         out.append(np.asarray(tf.text[int(st[r]):int(st[r + take])]).tobytes())
         i += take
     return b"".join(out)
+
+
+DUMP_CHUNKS = 16           # --dump-outputs: chunks whose text and descriptors are written (at most)
+DUMP_EDGE_BYTES = 384 << 10   # ... the first and the last this many bytes of each (float32: 4 B per byte)
+DUMP_BUDGET = 60_000_000   # bytes one run writes in all (kept under 64 MB), shared by its ranks and shards
+
+
+def dump_shard(d, shard, suffix="", budget=DUMP_BUDGET):
+    """What a caller of the shard's last run receives, as d/<name><suffix>.npy (--dump-outputs):
+    every chunk's records, produced bytes, status, flags and end bit (float64, exact), and for a
+    fixed sample of chunks (the first, the last, the rest drawn with seed 0; DUMP_CHUNKS of them, or
+    as many as the largest chunk's share lets `budget` bytes hold) the record descriptors (float32:
+    offsets within a chunk, < 2^24) and, when the output is one resident batch, the first and last
+    DUMP_EDGE_BYTES of the decompressed text (float32).  ~55 MB at the default workload: 16 x 768 KiB
+    x 4 B of text, 2.6 MB of descriptors, 2 MB of per-chunk arrays."""
+    os.makedirs(d, exist_ok=True)
+    r = shard.results()
+    for k, v in r.items():
+        np.save(os.path.join(d, f"chunk_{k}{suffix}.npy"), v.astype(np.float64))
+    n = shard.n
+    if n == 0:
+        return
+    per_chunk = int((4 * np.minimum(r["produced"], 2 * DUMP_EDGE_BYTES) + 16 * r["records"]).max()) + 1024
+    want = int(max(2, min(DUMP_CHUNKS, (budget - 5 * 8 * n - 4096) // per_chunk)))
+    pick = np.unique(np.concatenate([[0, n - 1], np.random.default_rng(0).choice(n, min(n, want - 2), replace=False)]))
+    np.save(os.path.join(d, f"sample_chunks{suffix}.npy"), pick.astype(np.float64))
+    for k in pick:
+        k = int(k)
+        np.save(os.path.join(d, f"descriptors_chunk{k}{suffix}.npy"), shard.chunk_records(k).astype(np.float32))
+        if shard.batches == 1:
+            t = shard.chunk_bytes(k)
+            if t.size > 2 * DUMP_EDGE_BYTES:
+                t = np.concatenate([t[:DUMP_EDGE_BYTES], t[-DUMP_EDGE_BYTES:]])
+            np.save(os.path.join(d, f"text_chunk{k}{suffix}.npy"), t.astype(np.float32))
+    if shard.batches != 1:
+        log(f"[bench] --dump-outputs: {shard.batches} output batches stream through one buffer: no text written")
 
 
 def wave_slots(dev):
@@ -1040,6 +1089,13 @@ def main():
     ap.add_argument("--steps", type=int, default=3)
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--workload", default="50gb", choices=["50gb", "1m"])
+    ap.add_argument("--full", action="store_true",
+                    help="also run the side measurements (CPU baseline, ingest, enumerator and per-chunk legs; "
+                         "--paired: the pair chunks' byte comparison and the decode + check only timing); a plain "
+                         "run only sets up, warms up, times the steps and prints the line")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last step computed as DIR/<name>.npy (float32 / "
+                         "float64, under 64 MB: per-chunk results and a fixed sample of chunks' text and descriptors)")
     ap.add_argument("--chunk", type=int, default=10000)
     # the 50 GB member repeats one segment of distinct text: 10.5 M records (~4 GB of text, ~1 GB of
     # gzip) x 51 = ~50 GB gz, ~535 M records (r01: a 1 GB segment x 203)
@@ -1052,7 +1108,7 @@ def main():
     ap.add_argument("--host-threads", type=int, default=16)
     ap.add_argument("--shm-dir", default="/dev/shm",
                     help="N > 1: where local rank 0 publishes the built input member for the other ranks")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
     ap.add_argument("--ingest-piece-gib", type=float, default=8,
                     help="ingest leg: compressed GiB per pipelined piece (ppg_file_decompress_all piece_bytes)")
     ap.add_argument("--ix-piece-kib", type=float, default=0,
@@ -1094,14 +1150,14 @@ def main():
                     help="side measurement: an empty line after every record, so every chunk takes the declined-chunk "
                          "parse (ppg_parse_chain; PPG_PARSE_CHAIN=0: the byte-serial lane) -- not the metric's workload")
     ap.add_argument("--no-ingest", action="store_true",
-                    help="skip the end-to-end leg (N = 1): DecompressAll straight from the .gz file on disk (host "
+                    help="--full: skip the end-to-end leg (N = 1): DecompressAll straight from the .gz file on disk (host "
                          "ingest, PCIe-inclusive; reported under 'ingest', never as value)")
     ap.add_argument("--ingest", action="store_true", help=argparse.SUPPRESS)   # on by default since r02
     ap.add_argument("--no-enumerate", action="store_true",
-                    help="skip the enumerator leg (N = 1, after the ingest leg): every record's bytes and descriptor "
+                    help="--full: skip the enumerator leg (N = 1, after the ingest leg): every record's bytes and descriptor "
                          "landed in host memory through ppg_cursor (reported under 'enumerate', never as value)")
     ap.add_argument("--no-chunk-api", action="store_true",
-                    help="skip the per-chunk Decompress leg (N = 1): ppg_decompress_chunk from 1/8/64 host threads "
+                    help="--full: skip the per-chunk Decompress leg (N = 1): ppg_decompress_chunk from 1/8/64 host threads "
                          "(reported under 'decompress_chunk', never as value)")
     ap.add_argument("--enum-batch-gib", type=float, default=8.0, help="enumerator leg: text per cursor batch (GiB)")
     args = ap.parse_args()
@@ -1299,6 +1355,8 @@ def run_bench(args, dev, world, rank, local, dist_on, backend, xdev):
 
     # correctness of the run (size-independent checks; bit parity is tests/test_gpu_parity.py)
     r = shard.results()
+    if args.dump_outputs:
+        dump_shard(args.dump_outputs, shard, f"_rank{rank}" if world > 1 else "", DUMP_BUDGET // world)
     # per-rank evidence: every rank's own step time, inflate launch time,
     # output batches, chunks, waves and records, so an N > 1 curve can be diagnosed from its line
     per_rank = [{"rank": i, "ms_per_step": round(v[0], 3), "inflate_ms_per_step": round(v[1], 3),
@@ -1392,7 +1450,7 @@ def run_bench(args, dev, world, rank, local, dist_on, backend, xdev):
                      "note": "each rank's own clock over the timed steps (value uses the max over ranks, "
                              "barrier-bracketed); inflate/parse: HIP-event launch times of its shard"},
     }
-    if (dist_on or args.share > 1) and args.workload == "50gb" and not args.no_ingest and not args.blank_lines:
+    if args.full and (dist_on or args.share > 1) and args.workload == "50gb" and not args.no_ingest and not args.blank_lines:
         # end to end at N > 1 ("scaling limits are host file read and
         # PCIe H2D"): every rank streams its own [P[a].Input - 1, P[b].Input - 1] range of the member
         # from a file in page cache (LazyFileReader.cs:41-97's role) through ppg_file_decompress_all;
@@ -1400,8 +1458,9 @@ def run_bench(args, dev, world, rank, local, dist_on, backend, xdev):
         shard = comp = None
         torch.cuda.empty_cache()
         line["ingest"] = dist_ingest_run(tf, args, ctx, a, b, rank, world, dist_on, xdev)
-    args.ingest = world == 1 and args.workload == "50gb" and not args.no_ingest and not args.blank_lines and args.share == 1
-    chunk_legs = world == 1 and args.workload == "50gb" and not args.no_chunk_api and args.share == 1
+    args.ingest = (args.full and world == 1 and args.workload == "50gb" and not args.no_ingest and not args.blank_lines
+                   and args.share == 1)
+    chunk_legs = args.full and world == 1 and args.workload == "50gb" and not args.no_chunk_api and args.share == 1
     if rank == 0 and world == 1 and (args.ingest or args.create_index or chunk_legs):
         # the measured shard (~270 GB of HBM at configs[2]) is done with: the legs below get the device
         shard = comp = None
@@ -1431,7 +1490,7 @@ def run_bench(args, dev, world, rank, local, dist_on, backend, xdev):
             line["decompress_chunk"] = decompress_chunk_run(tf, ctx, r["records"])
         except (AssertionError, RuntimeError, pp.PpgError) as e:
             line["decompress_chunk"] = {"error": f"{type(e).__name__}: {e}"}
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         line["cpu_baseline"] = cpu_baseline(tf, ix_out, ix_in, nchunks, usable_cpus())
     if rank == 0:
         print(json.dumps(line), flush=True)

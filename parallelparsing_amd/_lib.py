@@ -186,6 +186,10 @@ def synth():
         s.ppg_synth_gzip.argtypes = [vp, i64, C.c_int, i64, C.c_int, vp, i64]
         s.ppg_synth_segment.restype = i64
         s.ppg_synth_segment.argtypes = [vp, i64, C.c_int, i64, C.c_int, vp, i64, P(C.c_uint32)]
+        s.ppg_synth_segment_pieces.restype = i64
+        s.ppg_synth_segment_pieces.argtypes = [vp, i64, C.c_int, i64, C.c_int, vp, i64, P(C.c_uint32), vp, i64]
+        s.ppg_synth_segment_blocks_pieces.restype = i64
+        s.ppg_synth_segment_blocks_pieces.argtypes = [vp, vp, i64, vp, i64, i64, C.c_int, vp, vp, i64]
         s.ppg_synth_tiled_frame.restype = None
         s.ppg_synth_tiled_frame.argtypes = [C.c_uint32, i64, i64, vp, vp]
         s.ppg_synth_segment_blocks.restype = i64

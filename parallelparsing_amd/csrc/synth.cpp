@@ -306,12 +306,18 @@ int64_t ppg_synth_gzip(const uint8_t *text, int64_t len, int level, int64_t piec
 // ---- tiled member -------------------------------------------------------------------------
 // Segment deflate: text deflated as pigz pieces, first piece without dictionary, every piece
 // closed by Z_SYNC_FLUSH (so the segment ends byte-aligned and references nothing before it).
-// seg_out receives the raw deflate bytes; returns their length.
-int64_t ppg_synth_segment(const uint8_t *text, int64_t len, int level, int64_t piece, int threads,
-                          uint8_t *seg_out, int64_t cap, uint32_t *crc_out) {
+// seg_out receives the raw deflate bytes; returns their length.  piece_len (may be null; piece_cap
+// entries) receives each piece's compressed length, for ppg_synth_segment_blocks_pieces; -1 if
+// piece_cap is short.  The text's CRC-32 is taken piece by piece on the same threads and joined
+// with crc32_combine (4 GB of text: seconds of one core otherwise).
+int64_t ppg_synth_segment_pieces(const uint8_t *text, int64_t len, int level, int64_t piece, int threads,
+                                 uint8_t *seg_out, int64_t cap, uint32_t *crc_out, int64_t *piece_len,
+                                 int64_t piece_cap) {
     if (piece <= 0) piece = len;
     int64_t np = (len + piece - 1) / piece;
+    if (piece_len && np > piece_cap) return -1;
     std::vector<std::vector<uint8_t>> parts((size_t)np);
+    std::vector<uLong> crcs((size_t)np);
     std::atomic<int64_t> next{0};
     std::atomic<int> bad{0};
     std::vector<std::thread> th;
@@ -323,6 +329,13 @@ int64_t ppg_synth_segment(const uint8_t *text, int64_t len, int level, int64_t p
                 int64_t lo = i * piece, hi = std::min(len, lo + piece);
                 int64_t dl = std::min<int64_t>(lo, 32768);
                 if (deflate_piece(text, lo, hi, text + lo - dl, (int)dl, level, 0, parts[i]) < 0) bad = 1;
+                uLong c = crc32(0L, Z_NULL, 0);
+                for (int64_t pos = lo; pos < hi;) {
+                    int64_t n = std::min<int64_t>(hi - pos, 1 << 30);
+                    c = crc32(c, text + pos, (uInt)n);
+                    pos += n;
+                }
+                crcs[(size_t)i] = c;
             }
         });
     }
@@ -333,18 +346,18 @@ int64_t ppg_synth_segment(const uint8_t *text, int64_t len, int level, int64_t p
     if (tot > cap) return -1;
     uint8_t *w = seg_out;
     for (auto &p : parts) { memcpy(w, p.data(), p.size()); w += p.size(); }
-    *crc_out = (uint32_t)crc32(0L, text, (uInt)0);
-    {
-        uLong c = 0;
-        int64_t pos = 0;
-        while (pos < len) {
-            int64_t n = std::min<int64_t>(len - pos, 1 << 30);
-            c = crc32(c, text + pos, (uInt)n);
-            pos += n;
-        }
-        *crc_out = (uint32_t)c;
+    uLong c = crc32(0L, Z_NULL, 0);
+    for (int64_t i = 0; i < np; i++) {
+        c = crc32_combine(c, crcs[(size_t)i], (z_off_t)(std::min(len, (i + 1) * piece) - i * piece));
+        if (piece_len) piece_len[i] = (int64_t)parts[(size_t)i].size();
     }
+    *crc_out = (uint32_t)c;
     return tot;
+}
+
+int64_t ppg_synth_segment(const uint8_t *text, int64_t len, int level, int64_t piece, int threads,
+                          uint8_t *seg_out, int64_t cap, uint32_t *crc_out) {
+    return ppg_synth_segment_pieces(text, len, level, piece, threads, seg_out, cap, crc_out, nullptr, 0);
 }
 
 // gzip header (10 B) and the tail that closes a tiled member: an empty final fixed block
@@ -360,19 +373,20 @@ void ppg_synth_tiled_frame(uint32_t seg_crc, int64_t seg_len, int64_t repeats, u
     put_le32(tail10 + 6, (uint32_t)((uint64_t)seg_len * (uint64_t)repeats));
 }
 
-// Deflate block ends of the segment (raw stream, no dictionary), found exactly as CreateIndex
-// sees them: inflate(Z_BLOCK) returns with data_type bit 128 (Core.cs:64,98).  Writes, per block
-// end, its bit position within the segment and its output position.  Returns the count.
-int64_t ppg_synth_segment_blocks(const uint8_t *seg, int64_t seg_len, int64_t text_len, int64_t *bit_end,
-                                 int64_t *out_end, int64_t cap) {
+// Deflate block ends of a raw stream seg[0, seg_len) whose history is dict[0, dlen) (dlen = 0:
+// none), found exactly as CreateIndex sees them: inflate(Z_BLOCK) returns with data_type bit 128
+// (Core.cs:64,98).  Appends (bit_base + bit position within seg, out_base + output position) per
+// block end to ev.
+static int scan_blocks(const uint8_t *seg, int64_t seg_len, const uint8_t *dict, int dlen, int64_t bit_base,
+                       int64_t out_base, std::vector<int64_t> &ev) {
     z_stream zs;
     memset(&zs, 0, sizeof zs);
     if (inflateInit2(&zs, -15) != Z_OK) return -1;
+    if (dlen > 0 && inflateSetDictionary(&zs, dict, (uInt)dlen) != Z_OK) { inflateEnd(&zs); return -1; }
     std::vector<uint8_t> win(1 << 20);
-    int64_t n = 0, totin = 0, totout = 0, pos = 0;
+    int64_t totin = 0, totout = 0, pos = 0;
     int ret = Z_OK;
     zs.avail_out = 0;
-    (void)text_len;
     for (;;) {
         if (zs.avail_in == 0) {  // every byte of the segment is consumed, so trailing empty blocks count
             int64_t k = std::min<int64_t>(seg_len - pos, 1 << 20);
@@ -387,11 +401,58 @@ int64_t ppg_synth_segment_blocks(const uint8_t *seg, int64_t seg_len, int64_t te
         totin -= zs.avail_in; totout -= zs.avail_out;
         if (ret != Z_OK && ret != Z_BUF_ERROR) { inflateEnd(&zs); return -1; }
         if ((zs.data_type & 128) && !(zs.data_type & 64)) {
-            if (n < cap) { bit_end[n] = 8 * totin - (zs.data_type & 7); out_end[n] = totout; }
-            n++;
+            ev.push_back(bit_base + 8 * totin - (zs.data_type & 7));
+            ev.push_back(out_base + totout);
         }
     }
     inflateEnd(&zs);
+    return 0;
+}
+
+// Deflate block ends of the segment (raw stream, no dictionary): per block end, its bit position
+// within the segment and its output position.  Returns the count (one serial pass).
+int64_t ppg_synth_segment_blocks(const uint8_t *seg, int64_t seg_len, int64_t text_len, int64_t *bit_end,
+                                 int64_t *out_end, int64_t cap) {
+    std::vector<int64_t> ev;
+    (void)text_len;
+    if (scan_blocks(seg, seg_len, nullptr, 0, 0, 0, ev) < 0) return -1;
+    const int64_t n = (int64_t)ev.size() / 2;
+    for (int64_t j = 0; j < std::min(n, cap); j++) { bit_end[j] = ev[2 * (size_t)j]; out_end[j] = ev[2 * (size_t)j + 1]; }
+    return n;
+}
+
+// The same list for a segment made by ppg_synth_segment_pieces(text, text_len, ..., piece, ...),
+// found piece by piece on `threads` threads: piece i is a raw stream of its own that ends byte
+// aligned (Z_SYNC_FLUSH) and whose history is the 32 KiB of text before it (deflate_piece's
+// dictionary).  The serial pass over the bench's 1 GB segment takes one core several seconds.
+int64_t ppg_synth_segment_blocks_pieces(const uint8_t *seg, const int64_t *piece_len, int64_t npieces,
+                                        const uint8_t *text, int64_t text_len, int64_t piece, int threads,
+                                        int64_t *bit_end, int64_t *out_end, int64_t cap) {
+    if (piece <= 0) piece = text_len;
+    std::vector<int64_t> base((size_t)npieces + 1, 0);
+    for (int64_t i = 0; i < npieces; i++) base[(size_t)i + 1] = base[(size_t)i] + piece_len[i];
+    std::vector<std::vector<int64_t>> ev((size_t)npieces);   // (bit, out) pairs of piece i, segment-relative
+    std::atomic<int64_t> next{0};
+    std::atomic<int> bad{0};
+    std::vector<std::thread> th;
+    for (int t = 0; t < std::max(1, threads); t++) {
+        th.emplace_back([&] {
+            for (;;) {
+                int64_t i = next.fetch_add(1);
+                if (i >= npieces) break;
+                const int64_t lo = i * piece, dl = std::min<int64_t>(lo, 32768), b0 = base[(size_t)i];
+                if (lo > text_len ||
+                    scan_blocks(seg + b0, piece_len[i], text + lo - dl, (int)dl, 8 * b0, lo, ev[(size_t)i]) < 0)
+                    bad = 1;
+            }
+        });
+    }
+    for (auto &x : th) x.join();
+    if (bad) return -1;
+    int64_t n = 0;
+    for (auto &e : ev)
+        for (size_t j = 0; j < e.size(); j += 2, n++)
+            if (n < cap) { bit_end[n] = e[j]; out_end[n] = e[j + 1]; }
     return n;
 }
 
@@ -404,15 +465,26 @@ int64_t ppg_synth_tiled_points(const uint8_t *text, int64_t text_len, int64_t se
                                const int64_t *bit_end, const int64_t *out_end, int64_t nblocks, uint32_t chunksize,
                                int64_t *p_output, int64_t *p_input, int32_t *p_bits, int32_t *p_off_len,
                                int64_t *p_at, int64_t cap) {
-    // '@' census of one segment at every block end (count and position of the last '@')
+    // '@' census of one segment at every block end (count and position of the last '@'); memchr:
+    // an '@' starts each record and little else, and a byte loop over 4 GB takes seconds
     std::vector<int64_t> at_blk((size_t)nblocks), last_at_blk((size_t)nblocks);
     int64_t cnt = 0, last = -1, x = 0;
+    auto census = [&](int64_t hi) {
+        while (x < hi) {
+            const uint8_t *q = (const uint8_t *)memchr(text + x, '@', (size_t)(hi - x));
+            if (!q) break;
+            cnt++;
+            last = q - text;
+            x = last + 1;
+        }
+        x = std::max(x, hi);
+    };
     for (int64_t b = 0; b < nblocks; b++) {
-        for (; x < out_end[b]; x++) if (text[x] == '@') { cnt++; last = x; }
+        census(out_end[b]);
         at_blk[(size_t)b] = cnt;
         last_at_blk[(size_t)b] = last;
     }
-    for (; x < text_len; x++) if (text[x] == '@') { cnt++; last = x; }
+    census(text_len);
     const int64_t seg_at = cnt, seg_last_at = last;
     int64_t np = 0;
     auto emit = [&](int64_t output, int64_t input, int bits, int64_t at_abs) -> int {

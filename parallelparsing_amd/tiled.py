@@ -45,8 +45,11 @@ class TiledFile:
         cap = n // 2 + (1 << 20)
         seg = np.empty(cap, np.uint8)
         crc = C.c_uint32()
-        m = S.ppg_synth_segment(C.c_void_p(self.text.ctypes.data), n, level, piece, threads,
-                                C.c_void_p(seg.ctypes.data), cap, C.byref(crc))
+        npieces = -(-n // piece) if piece > 0 else 1
+        plen = np.empty(npieces, np.int64)
+        m = S.ppg_synth_segment_pieces(C.c_void_p(self.text.ctypes.data), n, level, piece, threads,
+                                       C.c_void_p(seg.ctypes.data), cap, C.byref(crc),
+                                       C.c_void_p(plen.ctypes.data), npieces)
         assert m > 0
         self.seg = seg[:m].copy()
         self.seg_crc = crc.value
@@ -55,11 +58,13 @@ class TiledFile:
         S.ppg_synth_tiled_frame(self.seg_crc, n, repeats, C.c_void_p(self.header.ctypes.data),
                                 C.c_void_p(self.tail.ctypes.data))
         self.file_len = 10 + repeats * m + 10
-        # deflate block ends of the segment
+        # deflate block ends of the segment, piece by piece on the host threads (the same list as one
+        # serial ppg_synth_segment_blocks pass: tests/test_tiled.py)
         bcap = m // 16 + 1024
         be, oe = np.empty(bcap, np.int64), np.empty(bcap, np.int64)
-        nb = S.ppg_synth_segment_blocks(C.c_void_p(self.seg.ctypes.data), m, n, C.c_void_p(be.ctypes.data),
-                                        C.c_void_p(oe.ctypes.data), bcap)
+        nb = S.ppg_synth_segment_blocks_pieces(C.c_void_p(self.seg.ctypes.data), C.c_void_p(plen.ctypes.data),
+                                               npieces, C.c_void_p(self.text.ctypes.data), n, piece, threads,
+                                               C.c_void_p(be.ctypes.data), C.c_void_p(oe.ctypes.data), bcap)
         assert 0 < nb <= bcap
         self.block_bit_end, self.block_out_end = be[:nb].copy(), oe[:nb].copy()
         # point metadata for the whole member (windows/offsets are filled per range: windows())

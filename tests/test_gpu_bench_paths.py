@@ -46,6 +46,30 @@ def test_bench_launches_its_own_ranks_and_gathers_in_the_abi():
     assert "ppg_shard_gather_counts" in two["communicator"]["count_gather"]
 
 
+def test_plain_run_is_lean_and_dumps_its_outputs(tmp_path):
+    """A plain run prints the headline line without the --full legs, and --dump-outputs writes what
+    its last timed step computed: float arrays under 64 MB, the per-chunk records summing to the
+    line's record count, the sampled chunks' descriptors one row per record."""
+    import numpy as np
+    d = tmp_path / "out"
+    args = [a for a in SMALL if not a.startswith("--no-")]
+    line = _bench(args + ["--dump-outputs", str(d)])
+    assert not {"cpu_baseline", "ingest", "enumerate", "decompress_chunk"} & set(line)
+    assert line["steps"] == 1 and line["ms_per_step"] > 0
+    files = sorted(d.glob("*.npy"))
+    arrs = {f.stem: np.load(f) for f in files}
+    assert sum(f.stat().st_size for f in files) < 64e6
+    assert all(a.dtype in (np.float32, np.float64) for a in arrs.values())
+    rec = arrs["chunk_records"]
+    assert int(rec.sum()) == line["config"]["records"] and not arrs["chunk_status"].any()
+    pick = arrs["sample_chunks"].astype(int)
+    assert pick[0] == 0 and pick[-1] == rec.size - 1
+    for k in pick:
+        assert arrs[f"descriptors_chunk{k}"].shape == (int(rec[k]), 4)
+        assert arrs[f"text_chunk{k}"].size == min(int(arrs["chunk_produced"][k]), 2 * (384 << 10))
+    assert arrs["text_chunk0"][0] == ord("@") and arrs[f"text_chunk{pick[-1]}"][-1] == ord("\n")
+
+
 def test_bench_paired_two_ranks_same_pairs():
     args = ["--paired", "--seg-records", "100000", "--paired-repeats", "3", "--steps", "1", "--warmup", "1"]
     one = _bench(args)
@@ -131,7 +155,8 @@ def test_bench_world8_rehearsal_end_to_end_leg():
     """The N > 1 line's per-rank evidence and end-to-end leg, world 8 on the one
     GPU: every rank's own step / inflate times, batches and records; every rank streams its range of
     the member from a file through ppg_file_decompress_all, max-over-ranks seconds, records exact."""
-    args = [a for a in SMALL if a != "--no-ingest"] + ["--repeats", "16", "--gpus", "8", "--ingest-piece-gib", "0.25"]
+    args = [a for a in SMALL if a != "--no-ingest"] + ["--full", "--repeats", "16", "--gpus", "8",
+                                                       "--ingest-piece-gib", "0.25"]
     eight = _bench(args, timeout=420)
     pr = eight["per_rank"]["ranks"]
     assert [p["rank"] for p in pr] == list(range(8))

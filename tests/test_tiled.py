@@ -43,6 +43,24 @@ def test_tiled_points_equal_oracle(records, repeats, chunk, piece):
     assert o2.tobytes() == offs[s0:s0 + len(o2)].tobytes()
 
 
+@pytest.mark.parametrize("records,piece,threads", [(3000, 1 << 16, 4), (2500, 100_000, 3), (700, 1 << 20, 2)])
+def test_block_list_by_pieces_equals_the_serial_pass(records, piece, threads):
+    """TiledFile finds the segment's deflate block ends piece by piece on threads
+    (ppg_synth_segment_blocks_pieces, each piece inflated with the 32 KiB of text before it as its
+    history): the same list as one serial inflate(Z_BLOCK) pass over the whole segment, and the
+    per-piece CRC-32s joined equal the text's."""
+    import ctypes as C
+    from parallelparsing_amd._lib import synth
+    tf = TiledFile(records, 2, 500, piece=piece, threads=threads)
+    assert tf.seg_crc == zlib.crc32(tf.text.tobytes())
+    cap = tf.block_bit_end.size + 8
+    be, oe = np.empty(cap, np.int64), np.empty(cap, np.int64)
+    nb = synth().ppg_synth_segment_blocks(C.c_void_p(tf.seg.ctypes.data), tf.seg.size, tf.text.size,
+                                          C.c_void_p(be.ctypes.data), C.c_void_p(oe.ctypes.data), cap)
+    assert nb == tf.block_bit_end.size >= -(-tf.text.size // piece)
+    assert np.array_equal(be[:nb], tf.block_bit_end) and np.array_equal(oe[:nb], tf.block_out_end)
+
+
 @pytest.mark.parametrize("records,repeats,chunk,per", [(3000, 5, 1000, 3), (2500, 4, 5000, 8)])
 def test_side_points_are_block_starts(records, repeats, chunk, per):
     """TiledFile.side_points (ppg_shard_set_split's input in bench.py): every side point is a deflate

@@ -10,7 +10,7 @@
 # bench steps extra bench.py arguments with '_' for a space (e.g. stamps:--share_8).
 #   gputest[:<k1,k2,...>]       pytest -m gpu (all, or the tests matching any k)   -> gputest.txt
 #   smoke                       __graft_entry__.smoke()                            -> smoke.txt
-#   bench                       the default bench line (python bench.py)           -> bench_default.json
+#   bench                       the bench line with every leg (bench.py --full)    -> bench_default.json
 #   profile                     rocprofv3 kernel stats + FETCH/WRITE passes, summarised into
 #                               profiles/<tag>_bench*.{json,csv} and profiles/traffic.json
 #   stalls                      the stall PMC passes -> profiles/<tag>_inflate_stalls.json + inflate_stalls.json
@@ -49,7 +49,7 @@ run_step() {
     timeout -k 10 180 python -u -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.txt 2>&1 || { tail -5 $O/smoke.txt; return 1; }
     tail -1 $O/smoke.txt ;;
   bench)
-    timeout -k 10 500 python3 -u bench.py $xa > $O/bench_default.json 2> $O/bench_default.log || return $?
+    timeout -k 10 500 python3 -u bench.py --full $xa > $O/bench_default.json 2> $O/bench_default.log || return $?
     line $O/bench_default.json ;;
   profile)
     bash tools/profile_round.sh || return $?
@@ -65,11 +65,11 @@ run_step() {
     timeout -k 10 300 python3 -u bench.py --create-index --steps 2 --warmup 1 $NOLEGS > $O/create_index.json 2> $O/create_index.log || return $?
     tail -c 400 $O/create_index.json ;;
   paired)
-    timeout -k 10 400 python3 -u bench.py --paired --steps 3 --warmup 1 $PAIRED_ARGS > $O/paired.json 2> $O/paired.log || return $?
+    timeout -k 10 400 python3 -u bench.py --full --paired --steps 3 --warmup 1 $PAIRED_ARGS > $O/paired.json 2> $O/paired.log || return $?
     line $O/paired.json ;;
   w8)
     # (r06: with the N > 1 end-to-end leg; --no-ingest in W8_ARGS skips it)
-    PPG_BENCH_ONE_DEVICE=1 PPG_DIST_BACKEND=gloo timeout -k 10 900 python3 -u bench.py --gpus 8 --steps 2 --warmup 1 \
+    PPG_BENCH_ONE_DEVICE=1 PPG_DIST_BACKEND=gloo timeout -k 10 900 python3 -u bench.py --full --gpus 8 --steps 2 --warmup 1 \
       --no-cpu-baseline --no-enumerate --no-chunk-api $W8_ARGS $xa > $O/w8.json 2> $O/w8.log || { tail -20 $O/w8.log; return 1; }
     line $O/w8.json ;;
   shares)
@@ -90,7 +90,7 @@ run_step() {
   e2eshares)   # rank 0's share of an N-way split, resident AND end to end from a file (r06)
     mkdir -p $O/shares
     for n in ${SHARES-2 4 8}; do
-      timeout -k 10 400 python3 -u bench.py --steps 3 --warmup 1 --no-cpu-baseline --share $n $xa > $O/shares/e2e$n.json 2> $O/shares/e2e$n.log || return $?
+      timeout -k 10 400 python3 -u bench.py --full --steps 3 --warmup 1 --no-cpu-baseline --share $n $xa > $O/shares/e2e$n.json 2> $O/shares/e2e$n.log || return $?
       line $O/shares/e2e$n.json
       python3 -c "import json,sys; d=[json.loads(l) for l in open(sys.argv[1]) if l.startswith('{')][-1]; i=d.get('ingest',{}); print({k: i.get(k) for k in ('records_per_s','compressed_GBps','seconds_max_over_ranks','piece_GiB','waves_per_chunk','error')})" $O/shares/e2e$n.json
     done ;;
@@ -104,7 +104,7 @@ run_step() {
       > $O/$st.json 2> $O/$st.log || return $?
     grep PPG_STAMPS $O/$st.log | tail -4 ;;
   chunkapi)
-    timeout -k 10 400 python3 -u bench.py --steps 1 --warmup 0 --no-cpu-baseline --no-ingest --no-enumerate $xa \
+    timeout -k 10 400 python3 -u bench.py --full --steps 1 --warmup 0 --no-cpu-baseline --no-ingest --no-enumerate $xa \
       > $O/chunkapi.json 2> $O/chunkapi.log || return $?
     python3 -c "import json,sys; d=json.loads([l for l in open(sys.argv[1]) if l.startswith('{')][-1]); c=d.get('decompress_chunk', {}); print(json.dumps(c)[:1500])" $O/chunkapi.json ;;
   latency)
