@@ -246,6 +246,49 @@ int ppg_shard_set_keys(ppg_shard *sh, int64_t *dev_keys, int64_t cap);
  * none attached, attached after that run, or the run failed). */
 int ppg_shard_keys_ready(ppg_shard *sh);
 
+/* ---- packed reads: 2-bit sequences, an N mask and qualities as a structure of arrays ----
+ * What a read consumer (a k-mer counter, an aligner) builds from every FastqRecord.Sequence /
+ * .Quality (Common/FastqRecord.cs; Parsing.cs:41-47 slices them), made on the GPU from the resident
+ * output and descriptors.  Records are numbered as above (ppg_shard_record_base[k] + j); records
+ * the reference parses twice (key -2) are included, a consumer drops them by their keys.
+ * For record j with descriptor (n1,n2,n3,n4) relative to raw_k:
+ *   L_j = n2 - n1 - 1   the Sequence slice [n1+1, n2) exactly (a CRLF file's '\r' is part of it);
+ *   P_j = 32 * ceil(L_j / 32);  seq_off[0] = 0, seq_off[j+1] = seq_off[j] + P_j (int64, in bases);
+ *   seq_len[j] = L_j (uint32).
+ * Base i < L_j has position b = seq_off[j] + i and byte c = raw_k[n1+1+i]:
+ *   bases  uint32 words of 16 bases: bits [2(b&15), 2(b&15)+2) of bases[b>>4] = A 0, C 1, G 2, T 3
+ *          (upper case only; any other byte gives 0);
+ *   mask   uint32 words of 32 bases: bit b&31 of mask[b>>5] = 1 iff c is none of ACGT;
+ *   qual   bytes (optional): qual[b] = raw_k[n3+1+i] if n3+1+i < n4, else 0 -- the Quality string,
+ *          cut or zero-filled to the sequence's length for a malformed record.
+ * Positions L_j <= i < P_j are 0 in all planes, and every word / byte below seq_off[nrecords] is
+ * written: the planes are a function of the text alone.  Every record starts on a 32-base unit
+ * (8 B of bases, one mask word, 32 B of qual).  Derived from the formats, per 150 bp record:
+ * 401 B of text + descriptors, ~232 B packed with qualities, ~72 B without.
+ * Buffers are caller device memory on this GPU, written on the ctx stream: dev_seq_off rec_cap + 1
+ * entries (8-byte aligned), dev_seq_len rec_cap, dev_bases base_cap / 16 words (8-byte aligned),
+ * dev_mask base_cap / 32 words, dev_qual base_cap bytes (16-byte aligned) or NULL for no quality
+ * plane; base_cap counts bases and is a multiple of 32.  PPG_BUF_ERROR when the records or the
+ * padded bases exceed the caps: nothing is written then.  PPG_ARG_ERROR for a NULL shard, one that
+ * has not run, a base_cap that is no multiple of 32, misaligned or missing planes.
+ *  ppg_shard_seq_bases     after a run of any number of batches (the descriptors stay resident):
+ *                          the sum of P_j and the record count -- the caps a pack needs.
+ *  ppg_shard_pack_seq      a one-batch shard after its run, blocking like the keys call above
+ *                          (PPG_ARG_ERROR on a multi-batch shard); *total_bases = seq_off[records].
+ *  ppg_shard_set_seqpack   any number of batches: from the next run on every batch is packed while
+ *                          its output is resident, record numbers and base offsets carried across
+ *                          batches.  All pointers NULL and caps 0 turn it off.
+ *  ppg_shard_seqpack_ready 1 when the last run filled the buffers (*total_bases: their padded
+ *                          bases), else 0: none attached, attached after that run, or it failed
+ *                          (PPG_ARG_ERROR, a negative value, for a NULL shard). */
+int ppg_shard_seq_bases(ppg_shard *sh, int64_t *total_bases, int64_t *records);
+int ppg_shard_pack_seq(ppg_shard *sh, int64_t *dev_seq_off, uint32_t *dev_seq_len, int64_t rec_cap,
+                       uint32_t *dev_bases, uint32_t *dev_mask, uint8_t *dev_qual, int64_t base_cap,
+                       int64_t *total_bases);
+int ppg_shard_set_seqpack(ppg_shard *sh, int64_t *dev_seq_off, uint32_t *dev_seq_len, int64_t rec_cap,
+                          uint32_t *dev_bases, uint32_t *dev_mask, uint8_t *dev_qual, int64_t base_cap);
+int ppg_shard_seqpack_ready(ppg_shard *sh, int64_t *total_bases);
+
 /* Device-resident per-chunk record counts (int64[n]) copied to caller device memory on this
  * GPU (the input of the cross-GPU all-gather). */
 int ppg_shard_counts_to_device(ppg_shard *sh, int64_t *dev_dst);
@@ -305,6 +348,23 @@ int ppg_cursor_open(ppg_ctx *ctx, const ppg_index *ix, const char *gz_path, int3
 int ppg_cursor_next(ppg_cursor *c, ppg_batch *b);
 int32_t ppg_cursor_batches(const ppg_cursor *c);
 void ppg_cursor_close(ppg_cursor *c);
+
+/* The packed enumerator: as ppg_cursor_open, but a batch carries packed reads (the format of
+ * "packed reads" above, seq_off batch-relative from 0) instead of text + descriptors, so ~232 B
+ * (planes bit 0 = 1: with qualities) or ~72 B (planes = 0) per 150 bp record cross PCIe instead of
+ * 401 B.  In a ppg_batch of such a cursor text and desc are NULL; first_chunk, nchunks, record_base,
+ * nrecords, raw_off and rec_off are filled as for a text cursor.
+ *  ppg_cursor_packed          the current batch's planes in pinned host memory (valid until the
+ *                             next ppg_cursor_next; any pointer may be NULL; *qual = NULL without
+ *                             the quality plane) and its padded bases;
+ *  ppg_cursor_packed_offsets  its nrecords + 1 offsets copied to the caller (cap entries;
+ *                             PPG_BUF_ERROR when fewer).
+ * Both return PPG_ARG_ERROR on a text cursor and before the first ppg_cursor_next. */
+int ppg_cursor_open_packed(ppg_ctx *ctx, const ppg_index *ix, const char *gz_path, int32_t first, int32_t n,
+                           int64_t batch_bytes, int threads, int32_t planes, ppg_cursor **out);
+int ppg_cursor_packed(const ppg_cursor *c, uint32_t **bases, uint32_t **mask, uint8_t **qual, uint32_t **seq_len,
+                      int64_t *total_bases);
+int ppg_cursor_packed_offsets(const ppg_cursor *c, int64_t *seq_off, int64_t cap);
 
 /* ======================= multi-GPU DecompressAll (one process per GPU) =======================
  * BatchedFASTQ's fan-out (BatchedFASTQ.cs:62-77: a task per chunk) becomes a fan-out over GPUs:

@@ -127,6 +127,13 @@ internal static unsafe class PpGpu
     [DllImport(Lib)] public static extern int ppg_shard_keys(nint shard, long* devKeys, long cap);
     [DllImport(Lib)] public static extern int ppg_shard_set_keys(nint shard, long* devKeys, long cap);
     [DllImport(Lib)] public static extern int ppg_shard_keys_ready(nint shard);
+    // packed reads: 2-bit bases, N mask, qualities (device planes; the format is in ppgpu.h)
+    [DllImport(Lib)] public static extern int ppg_shard_seq_bases(nint shard, out long totalBases, out long records);
+    [DllImport(Lib)] public static extern int ppg_shard_pack_seq(nint shard, long* devSeqOff, uint* devSeqLen, long recCap,
+        uint* devBases, uint* devMask, byte* devQual, long baseCap, out long totalBases);
+    [DllImport(Lib)] public static extern int ppg_shard_set_seqpack(nint shard, long* devSeqOff, uint* devSeqLen,
+        long recCap, uint* devBases, uint* devMask, byte* devQual, long baseCap);
+    [DllImport(Lib)] public static extern int ppg_shard_seqpack_ready(nint shard, out long totalBases);
     [DllImport(Lib)] public static extern int ppg_shard_counts_to_device(nint shard, long* devDst);
     [DllImport(Lib)] public static extern int ppg_shard_timing(nint shard, out float inflateMs, out float parseMs,
         out float totalMs);
@@ -142,6 +149,12 @@ internal static unsafe class PpGpu
     [DllImport(Lib)] public static extern int ppg_cursor_next(nint cursor, out PpgBatch batch);
     [DllImport(Lib)] public static extern int ppg_cursor_batches(nint cursor);
     [DllImport(Lib)] public static extern void ppg_cursor_close(nint cursor);
+    // the packed enumerator: batches of packed reads in pinned host memory (planes bit 0 = qualities)
+    [DllImport(Lib)] public static extern int ppg_cursor_open_packed(nint ctx, nint ix, string gzPath, int first, int n,
+        long batchBytes, int threads, int planes, out nint cursor);
+    [DllImport(Lib)] public static extern int ppg_cursor_packed(nint cursor, uint** bases, uint** mask, byte** qual,
+        uint** seqLen, out long totalBases);
+    [DllImport(Lib)] public static extern int ppg_cursor_packed_offsets(nint cursor, long* seqOff, long cap);
 
     // ---- multi-GPU DecompressAll: partition + count all-gather over RCCL inside the library ----
     [DllImport(Lib)] public static extern int ppg_comm_unique_id(byte* id /* 128 bytes */);

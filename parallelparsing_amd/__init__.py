@@ -443,6 +443,101 @@ class ChunkFuture:
                 pass
 
 
+class PackedReads:
+    """A packed read set (include/ppgpu.h "packed reads"): seq_off (int64, records + 1, in bases),
+    seq_len (records), bases (2 bits per base, 16 per word), mask (1 bit per base: not ACGT) and
+    qual (one byte per base, or None); every record starts on a 32-base unit.  The arrays are
+    either CUDA tensors on one device (int64; int32 views of the uint32 words; uint8) or numpy
+    arrays (int64, uint32, uint8).  sequence(j) / quality(j) read host arrays."""
+
+    _CODES = np.frombuffer(b"ACGT", np.uint8)
+
+    def __init__(self, seq_off, seq_len, bases, mask, qual=None, records=None, total_bases=None):
+        self.seq_off, self.seq_len, self.bases, self.mask, self.qual = seq_off, seq_len, bases, mask, qual
+        self.records = int(records) if records is not None else int(seq_len.shape[0])
+        self.total_bases = None if total_bases is None else int(total_bases)
+
+    @classmethod
+    def empty(cls, rec_cap, base_cap, quality=True, device=None):
+        """Planes for rec_cap records and base_cap bases (rounded up to a multiple of 32): CUDA
+        tensors on `device` (an int or torch.device), numpy arrays when device is None."""
+        rec_cap, base_cap = int(rec_cap), (int(base_cap) + 31) // 32 * 32
+        if device is None:
+            return cls(np.zeros(rec_cap + 1, np.int64), np.zeros(rec_cap, np.uint32), np.zeros(base_cap // 16, np.uint32),
+                       np.zeros(base_cap // 32, np.uint32), np.zeros(base_cap, np.uint8) if quality else None)
+        import torch
+        dev = torch.device("cuda", device) if isinstance(device, int) else torch.device(device)
+        mk = lambda n, dt: torch.zeros(max(int(n), 1), dtype=dt, device=dev)[:int(n)]   # noqa: E731
+        return cls(mk(rec_cap + 1, torch.int64), mk(rec_cap, torch.int32), mk(base_cap // 16, torch.int32),
+                   mk(base_cap // 32, torch.int32), mk(base_cap, torch.uint8) if quality else None)
+
+    @property
+    def on_device(self):
+        return hasattr(self.seq_off, "data_ptr")
+
+    @property
+    def rec_cap(self):
+        return int(self.seq_len.shape[0])
+
+    @property
+    def base_cap(self):
+        return 32 * int(self.mask.shape[0])
+
+    def _check_device(self, what):
+        import torch
+        planes = [self.seq_off, self.seq_len, self.bases, self.mask] + ([self.qual] if self.qual is not None else [])
+        dts = [torch.int64, torch.int32, torch.int32, torch.int32, torch.uint8]
+        for t, dt in zip(planes, dts):
+            if not (hasattr(t, "data_ptr") and t.is_cuda and t.dtype == dt and t.is_contiguous()):
+                raise ValueError(f"{what}: the planes must be contiguous CUDA tensors (int64, int32 words, uint8)")
+        if self.seq_off.numel() != self.rec_cap + 1 or self.bases.numel() != 2 * self.mask.numel() or \
+                (self.qual is not None and self.qual.numel() != self.base_cap):
+            raise ValueError(f"{what}: plane sizes do not agree (PackedReads.empty makes them)")
+
+    def _ptrs(self):
+        return (C.c_void_p(self.seq_off.data_ptr()), C.c_void_p(self.seq_len.data_ptr()), self.rec_cap,
+                C.c_void_p(self.bases.data_ptr()), C.c_void_p(self.mask.data_ptr()),
+                C.c_void_p(self.qual.data_ptr()) if self.qual is not None else None, self.base_cap)
+
+    def to_host(self):
+        """The same read set as numpy arrays (a copy; uint32 words), cut to its records and bases
+        when they are known."""
+        if not self.on_device:
+            return self
+        off = self.seq_off.cpu().numpy()
+        nb = self.total_bases if self.total_bases is not None else self.base_cap
+        nr = self.records
+        w = lambda t, n: t.cpu().numpy().view(np.uint32)[:n].copy()   # noqa: E731
+        return PackedReads(off[:nr + 1].copy(), w(self.seq_len, nr), w(self.bases, nb // 16), w(self.mask, nb // 32),
+                           self.qual.cpu().numpy()[:nb].copy() if self.qual is not None else None, nr, nb)
+
+    def _span(self, j):
+        if self.on_device:
+            raise ValueError("PackedReads: sequence / quality read host arrays (to_host() first)")
+        return int(self.seq_off[j]), int(self.seq_len[j])
+
+    def sequence(self, j):
+        """Record j's Sequence as bytes, every masked position as 'N'."""
+        b, L = self._span(j)
+        if L == 0:
+            return b""
+        P = (L + 31) // 32 * 32
+        words = np.asarray(self.bases[b >> 4:(b + P) >> 4], np.uint32)
+        codes = ((words[:, None] >> (2 * np.arange(16, dtype=np.uint32))) & 3).reshape(-1)[:L]
+        mw = np.asarray(self.mask[b >> 5:(b + P) >> 5], np.uint32)
+        m = ((mw[:, None] >> np.arange(32, dtype=np.uint32)) & 1).reshape(-1)[:L]
+        s = self._CODES[codes]
+        s[m != 0] = ord("N")
+        return s.tobytes()
+
+    def quality(self, j):
+        """Record j's quality bytes (the Quality string cut or zero-filled to the sequence's length)."""
+        if self.qual is None:
+            raise ValueError("PackedReads: no quality plane")
+        b, L = self._span(j)
+        return np.asarray(self.qual[b:b + L], np.uint8).tobytes()
+
+
 class Shard:
     """DecompressAll over index chunks [first, first+n) resident on one GPU (ppg_shard)."""
 
@@ -483,8 +578,8 @@ class Shard:
             self.dev.after_torch()
 
     def run(self):
-        if self._on_device:
-            self._torch_order()   # the caller may have rewritten comp since the last run
+        if self._on_device or getattr(self, "_seqpack", None) is not None:
+            self._torch_order()   # the caller may have rewritten comp (or the set_seqpack planes) since the last run
         check(lib.ppg_shard_run(self._h), "DecompressAll")
         return self
 
@@ -539,6 +634,52 @@ class Shard:
         self._keys = keys   # kept alive while the library may write it
         check(lib.ppg_shard_set_keys(self._h, C.c_void_p(keys.data_ptr()), keys.numel()), "set_keys")
         return self
+
+    def seq_bases(self):
+        """(padded bases, records) of the last run, any number of batches (ppg_shard_seq_bases):
+        the capacities a PackedReads of the whole shard needs."""
+        tot, rec = C.c_int64(), C.c_int64()
+        check(lib.ppg_shard_seq_bases(self._h, C.byref(tot), C.byref(rec)), "seq_bases")
+        return tot.value, rec.value
+
+    def pack_sequences(self, quality=True, packed=None):
+        """The packed reads of a one-batch shard after its run (ppg_shard_pack_seq), as a
+        PackedReads of CUDA tensors on this device: into `packed`, or into a new one sized by
+        seq_bases().  Ordered after torch's stream, complete on return."""
+        if packed is None:
+            tot, rec = self.seq_bases()
+            packed = PackedReads.empty(rec, tot, quality, self.dev.device)
+        packed._check_device("pack_sequences")
+        self.dev.after_torch()
+        tot = C.c_int64()
+        check(lib.ppg_shard_pack_seq(self._h, *packed._ptrs(), C.byref(tot)), "pack_sequences")
+        packed.records, packed.total_bases = self.total_records, tot.value
+        return packed
+
+    def set_seqpack(self, packed):
+        """From the next run on, every output batch packs its reads into `packed` (a PackedReads of
+        CUDA tensors on this device, sized for the whole shard: seq_bases() of an earlier run) while
+        its output is resident (ppg_shard_set_seqpack): works for shards of any number of batches.
+        None turns it off."""
+        if packed is None:
+            check(lib.ppg_shard_set_seqpack(self._h, None, None, 0, None, None, None, 0), "set_seqpack")
+            self._seqpack = None
+            return self
+        packed._check_device("set_seqpack")
+        self._seqpack = packed   # kept alive while the library may write it
+        self.dev.after_torch()
+        check(lib.ppg_shard_set_seqpack(self._h, *packed._ptrs()), "set_seqpack")
+        return self
+
+    @property
+    def seqpack_ready(self):
+        """Whether the last run filled the set_seqpack planes (their records / total_bases are then set)."""
+        tot = C.c_int64()
+        ok = lib.ppg_shard_seqpack_ready(self._h, C.byref(tot)) == 1
+        p = getattr(self, "_seqpack", None)
+        if ok and p is not None:
+            p.records, p.total_bases = self.total_records, tot.value
+        return ok
 
     def results(self):
         n = self.n
@@ -710,16 +851,27 @@ class Cursor:
     batches of whole chunks of at most batch_bytes of text, read and decoded on the GPU while the
     previous batch is consumed.  Iterating yields Batch objects; a batch's arrays are views of the
     library's pinned buffers and stay valid only until the next batch is requested (as a
-    FastqRecord is invalid after the next MoveNext, BatchedFASTQ.cs:56)."""
+    FastqRecord is invalid after the next MoveNext, BatchedFASTQ.cs:56).
 
-    def __init__(self, index, gzip_path, first=0, n=None, batch_bytes=1 << 30, threads=8, device=None):
+    packed=True opens the packed enumerator (ppg_cursor_open_packed): a batch then carries no text
+    and no descriptors but Batch.packed, a host PackedReads over the pinned planes (with the quality
+    plane when quality=True), so a fraction of the bytes crosses PCIe."""
+
+    def __init__(self, index, gzip_path, first=0, n=None, batch_bytes=1 << 30, threads=8, device=None,
+                 packed=False, quality=True):
         self.index = index
         self.dev = device or Device.default()
         if n is None:
             n = index.Count - 1 - first
+        self.packed, self.quality = bool(packed), bool(quality)
         h = C.c_void_p()
-        check(lib.ppg_cursor_open(self.dev.handle, index.handle, os.fsencode(gzip_path), int(first), int(n),
-                                  int(batch_bytes), int(threads), C.byref(h)), "ppg_cursor_open")
+        if packed:
+            check(lib.ppg_cursor_open_packed(self.dev.handle, index.handle, os.fsencode(gzip_path), int(first), int(n),
+                                             int(batch_bytes), int(threads), 1 if quality else 0, C.byref(h)),
+                  "ppg_cursor_open_packed")
+        else:
+            check(lib.ppg_cursor_open(self.dev.handle, index.handle, os.fsencode(gzip_path), int(first), int(n),
+                                      int(batch_bytes), int(threads), C.byref(h)), "ppg_cursor_open")
         self._h = h
 
     def __del__(self):
@@ -741,7 +893,27 @@ class Cursor:
         if rc == PPG_STREAM_END:
             return None
         check(rc, "ppg_cursor_next")
-        return Batch(b)
+        return Batch(b, self.packed_reads(b.nrecords) if self.packed else None)
+
+    def packed_reads(self, nrecords):
+        """The current batch's planes (ppg_cursor_packed / ppg_cursor_packed_offsets) as a host
+        PackedReads: views of pinned memory, valid until the next batch; seq_off is a copy."""
+        pb, pm, pq, pl = (C.c_void_p() for _ in range(4))
+        tot = C.c_int64()
+        check(lib.ppg_cursor_packed(self._h, C.byref(pb), C.byref(pm), C.byref(pq), C.byref(pl), C.byref(tot)),
+              "ppg_cursor_packed")
+        nr, nb = int(nrecords), tot.value
+        off = np.zeros(nr + 1, np.int64)
+        check(lib.ppg_cursor_packed_offsets(self._h, _ptr(off), off.size), "ppg_cursor_packed_offsets")
+
+        def view(p, ct, n):
+            if not n or not p.value:
+                return np.zeros(0, ct)
+            return np.ctypeslib.as_array(C.cast(p, C.POINTER(ct)), (n,))
+
+        qual = view(pq, C.c_uint8, nb) if pq.value else None
+        return PackedReads(off, view(pl, C.c_uint32, nr), view(pb, C.c_uint32, nb // 16), view(pm, C.c_uint32, nb // 32),
+                           qual, nr, nb)
 
     def __iter__(self):
         while True:
@@ -752,13 +924,18 @@ class Cursor:
 
 
 class Batch:
-    """One ppg_batch: text (uint8), raw_off / rec_off (int64, nchunks + 1), desc (nrecords x 4)."""
+    """One ppg_batch: text (uint8), raw_off / rec_off (int64, nchunks + 1), desc (nrecords x 4).  A
+    packed cursor's batch has text = desc = None and `packed`, a host PackedReads."""
 
-    def __init__(self, b):
+    def __init__(self, b, packed=None):
         self.first_chunk, self.nchunks = b.first_chunk, b.nchunks
         self.record_base, self.nrecords = b.record_base, b.nrecords
         self.raw_off = np.ctypeslib.as_array(b.raw_off, (b.nchunks + 1,))
         self.rec_off = np.ctypeslib.as_array(b.rec_off, (b.nchunks + 1,))
+        self.packed = packed
+        if packed is not None or not b.text:
+            self.text = self.desc = None
+            return
         nt = int(self.raw_off[-1])
         self.text = np.ctypeslib.as_array(C.cast(b.text, C.POINTER(C.c_uint8)), (max(nt, 1),))[:nt]
         nd = 4 * int(b.nrecords)

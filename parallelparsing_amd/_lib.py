@@ -117,6 +117,13 @@ _SIGS = {
     "ppg_cursor_next": (C.c_int, [vp, vp]),
     "ppg_cursor_batches": (i32, [vp]),
     "ppg_cursor_close": (None, [vp]),
+    "ppg_shard_seq_bases": (C.c_int, [vp, P(i64), P(i64)]),
+    "ppg_shard_pack_seq": (C.c_int, [vp, vp, vp, i64, vp, vp, vp, i64, P(i64)]),
+    "ppg_shard_set_seqpack": (C.c_int, [vp, vp, vp, i64, vp, vp, vp, i64]),
+    "ppg_shard_seqpack_ready": (C.c_int, [vp, P(i64)]),
+    "ppg_cursor_open_packed": (C.c_int, [vp, vp, C.c_char_p, i32, i32, i64, C.c_int, i32, P(vp)]),
+    "ppg_cursor_packed": (C.c_int, [vp, P(vp), P(vp), P(vp), P(vp), P(i64)]),
+    "ppg_cursor_packed_offsets": (C.c_int, [vp, vp, i64]),
     "ppg_comm_unique_id": (C.c_int, [vp]),
     "ppg_comm_init": (C.c_int, [vp, i32, i32, vp, P(vp)]),
     "ppg_comm_from_rccl": (C.c_int, [vp, vp, i32, i32, P(vp)]),

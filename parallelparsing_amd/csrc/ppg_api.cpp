@@ -54,6 +54,30 @@ hipError_t ppg_launch_record_keys(hipStream_t s, const uint8_t *out, const PpgIn
                                   const PpgInflateResult *ires, const uint8_t *offs, const PpgOffsetRef *oref,
                                   const PpgParseInfo *info, const uint64_t *base, const uint32_t *recs, int64_t *keys,
                                   int n);
+hipError_t ppg_launch_pack_raw(hipStream_t s, const uint8_t *out, const PpgInflateJob *jobs, const PpgInflateResult *ires,
+                               const uint8_t *offs, const PpgOffsetRef *oref, const int64_t *raw_off, uint8_t *dst,
+                               int n, int blocks);
+// launchers (ppg_seqpack.hip).  Weak references: libppgpu.so always links that object, but the
+// host-only sanitizer build (tests/native) links these translation units with the kernel objects of
+// inflate / parse / index alone; there the packed-read entry points fail with PPG_UNSUPPORTED
+// (seq_linked) instead of the link failing.  There is no other implementation to fall back to.
+#define PPG_WEAK __attribute__((weak))
+PPG_WEAK hipError_t ppg_launch_seq_totals(hipStream_t s, const PpgInflateResult *ires, const PpgParseInfo *info,
+                                          const uint64_t *base, const uint32_t *recs, uint64_t *ctot, int n);
+PPG_WEAK hipError_t ppg_launch_seq_scan(hipStream_t s, const uint64_t *ctot, uint64_t *cbase, uint64_t *host_total,
+                                        int n);
+PPG_WEAK hipError_t ppg_launch_seq_offsets(hipStream_t s, const PpgInflateResult *ires, const PpgParseInfo *info,
+                                           const uint64_t *base, const uint32_t *recs, const uint64_t *cbase,
+                                           int64_t carry, int64_t *seq_off, uint32_t *seq_len, int n);
+PPG_WEAK hipError_t ppg_launch_seq_pack(hipStream_t s, const uint8_t *out, const PpgInflateJob *jobs,
+                                        const PpgInflateResult *ires, const uint8_t *offs, const PpgOffsetRef *oref,
+                                        const PpgParseInfo *info, const uint64_t *base, const uint32_t *recs,
+                                        const uint64_t *cbase, const int64_t *seq_off, const uint32_t *seq_len,
+                                        int64_t carry, uint64_t total, uint32_t *bases, uint32_t *mask, uint8_t *qual,
+                                        int n);
+static bool seq_linked() {
+    return ppg_launch_seq_totals && ppg_launch_seq_scan && ppg_launch_seq_offsets && ppg_launch_seq_pack;
+}
 
 namespace {
 
@@ -652,6 +676,54 @@ void shard_reset(ppg_shard *sh) {
     sh->ran = 0;
 }
 
+// ---- packed reads (ppg_seqpack.hip) ----
+int shard_seq_reserve(ppg_shard *sh, int64_t nchunks) {
+    HIPCHK(sh->sp_ctot.alloc((size_t)nchunks + 1));
+    HIPCHK(sh->sp_cbase.alloc((size_t)nchunks + 1));
+    HIPCHK(sh->sp_htot.alloc(8));
+    return PPG_OK;
+}
+
+int shard_seq_layout(ppg_shard *sh, int32_t b0, int32_t b1, const uint32_t *recs, int64_t *total) {
+    hipStream_t s = shard_stream(sh);
+    const int nb = b1 - b0;
+    if (!seq_linked()) return PPG_UNSUPPORTED;
+    if (int rc = shard_seq_reserve(sh, std::max<int64_t>(nb, sh->n))) return rc;   // once: every batch fits
+    HIPCHK(ppg_launch_seq_totals(s, sh->res.p + b0, sh->info.p + b0, sh->base.p + b0, recs, sh->sp_ctot.p, nb));
+    HIPCHK(ppg_launch_seq_scan(s, sh->sp_ctot.p, sh->sp_cbase.p, (uint64_t *)sh->sp_htot.p, nb));
+    HIPCHK(hipStreamSynchronize(s));
+    *total = (int64_t)*(volatile uint64_t *)sh->sp_htot.p;
+    return PPG_OK;
+}
+
+int shard_seq_pack(ppg_shard *sh, int32_t b0, int32_t b1, const uint32_t *recs, int64_t carry, int64_t total,
+                   int64_t *seq_off, uint32_t *seq_len, uint32_t *bases, uint32_t *mask, uint8_t *qual) {
+    hipStream_t s = shard_stream(sh);
+    const int nb = b1 - b0;
+    if (!seq_linked()) return PPG_UNSUPPORTED;
+    HIPCHK(ppg_launch_seq_offsets(s, sh->res.p + b0, sh->info.p + b0, sh->base.p + b0, recs, sh->sp_cbase.p, carry,
+                                  seq_off, seq_len, nb));
+    HIPCHK(ppg_launch_seq_pack(s, sh->out.p, sh->jobs.p + b0, sh->res.p + b0, sh->offs.p, sh->oref.p + b0,
+                               sh->info.p + b0, sh->base.p + b0, recs, sh->sp_cbase.p, seq_off, seq_len, carry,
+                               (uint64_t)total, bases, mask, qual, nb));
+    return PPG_OK;
+}
+
+// batch_collect's hook: the batch's tot records go to shard record numbers [total_records, + tot),
+// their bases continue from the batches before.  Nothing is written when a cap would be exceeded.
+static int seq_hook(ppg_shard *sh, int32_t b0, int32_t b1, int64_t tot) {
+    if (sh->total_records == 0) sh->sp_total = 0;   // the run's first batch
+    const uint32_t *recs = sh->recs.p + 4 * (uint64_t)sh->total_records;
+    int64_t total = 0;
+    if (int rc = shard_seq_layout(sh, b0, b1, recs, &total)) return rc;
+    if (sh->total_records + tot > sh->sp_rec_cap || sh->sp_total + total > sh->sp_base_cap) return PPG_BUF_ERROR;
+    if (int rc = shard_seq_pack(sh, b0, b1, recs, sh->sp_total, total, sh->sp_off + sh->total_records,
+                                sh->sp_len + sh->total_records, sh->sp_bases, sh->sp_mask, sh->sp_qual))
+        return rc;
+    sh->sp_total += total;
+    return PPG_OK;
+}
+
 // Enqueue one batch [b0, b1) on the shard's stream, with no host synchronisation: inflate (+ the
 // fused newline census), per-chunk counts and their scan, the record total into pinned host
 // memory, then the descriptors, whose writes stop at the descriptor buffer's size.
@@ -733,6 +805,9 @@ int batch_collect(ppg_shard *sh, int32_t b0, int32_t b1, float &total_ms) {
                                       sh->info.p + b0, sh->base.p + b0, sh->recs.p + r0,
                                       sh->keys_dev + sh->total_records, nb));
     }
+    // packed reads of the batch, likewise while its output is resident (ppg_shard_set_seqpack)
+    if (sh->sp_off)
+        if (int rc = seq_hook(sh, b0, b1, (int64_t)tot)) return rc;
     sh->t_inflate += a;
     sh->t_parse += b + c;
     total_ms += a + b + c;
@@ -780,8 +855,10 @@ static int shard_run(ppg_shard *sh) {
 int ppg_shard_run(ppg_shard *sh) {
     if (!sh) return PPG_ARG_ERROR;
     sh->keys_written = 0;
+    sh->sp_written = 0;
     sh->last_rc = shard_run(sh);
     sh->keys_written = sh->last_rc == PPG_OK && sh->keys_dev != nullptr;
+    sh->sp_written = sh->last_rc == PPG_OK && sh->sp_off != nullptr;
     return sh->last_rc;
 }
 
@@ -995,6 +1072,140 @@ int ppg_shard_keys(ppg_shard *sh, int64_t *dev_keys, int64_t cap) {
                                   sh->recs.p, dev_keys, sh->n));
     HIPCHK(hipStreamSynchronize(s));
     return PPG_OK;
+}
+
+// ---- packed reads: the keys entry points' counterparts ----
+static bool seq_args_ok(const int64_t *off, const uint32_t *len, int64_t rec_cap, const uint32_t *bases,
+                        const uint32_t *mask, const uint8_t *qual, int64_t base_cap) {
+    // a unit is stored as one 8-B word of bases and 32 B of qualities: the planes' alignment
+    return off && len && bases && mask && rec_cap >= 0 && base_cap >= 0 && base_cap % 32 == 0 &&
+           ((uintptr_t)off & 7) == 0 && ((uintptr_t)len & 3) == 0 && ((uintptr_t)bases & 7) == 0 &&
+           ((uintptr_t)mask & 3) == 0 && ((uintptr_t)qual & 15) == 0;
+}
+
+int ppg_shard_seq_bases(ppg_shard *sh, int64_t *total_bases, int64_t *records) {
+    if (!sh || !sh->ran) return PPG_ARG_ERROR;
+    if (!seq_linked()) return PPG_UNSUPPORTED;
+    HIPCHK(hipSetDevice(sh->ctx->device));
+    hipStream_t s = shard_stream(sh);
+    if (int rc = shard_seq_reserve(sh, sh->n)) return rc;
+    // every batch's descriptors are resident, each with record bases relative to its own first record
+    for (auto [b0, b1] : sh->batches)
+        HIPCHK(ppg_launch_seq_totals(s, sh->res.p + b0, sh->info.p + b0, sh->base.p + b0,
+                                     sh->recs.p + 4 * (uint64_t)sh->h_base[(size_t)b0], sh->sp_ctot.p + b0, b1 - b0));
+    HIPCHK(ppg_launch_seq_scan(s, sh->sp_ctot.p, sh->sp_cbase.p, (uint64_t *)sh->sp_htot.p, sh->n));
+    HIPCHK(hipStreamSynchronize(s));
+    if (total_bases) *total_bases = (int64_t)*(volatile uint64_t *)sh->sp_htot.p;
+    if (records) *records = sh->total_records;
+    return PPG_OK;
+}
+
+int ppg_shard_pack_seq(ppg_shard *sh, int64_t *dev_seq_off, uint32_t *dev_seq_len, int64_t rec_cap,
+                       uint32_t *dev_bases, uint32_t *dev_mask, uint8_t *dev_qual, int64_t base_cap,
+                       int64_t *total_bases) {
+    if (!sh || !sh->ran || sh->batches.size() != 1 ||
+        !seq_args_ok(dev_seq_off, dev_seq_len, rec_cap, dev_bases, dev_mask, dev_qual, base_cap))
+        return PPG_ARG_ERROR;
+    HIPCHK(hipSetDevice(sh->ctx->device));
+    int64_t total = 0;
+    if (int rc = shard_seq_layout(sh, 0, sh->n, sh->recs.p, &total)) return rc;
+    if (total_bases) *total_bases = total;
+    if (sh->total_records > rec_cap || total > base_cap) return PPG_BUF_ERROR;
+    if (int rc = shard_seq_pack(sh, 0, sh->n, sh->recs.p, 0, total, dev_seq_off, dev_seq_len, dev_bases, dev_mask,
+                                dev_qual))
+        return rc;
+    HIPCHK(hipStreamSynchronize(shard_stream(sh)));
+    return PPG_OK;
+}
+
+int ppg_shard_set_seqpack(ppg_shard *sh, int64_t *dev_seq_off, uint32_t *dev_seq_len, int64_t rec_cap,
+                          uint32_t *dev_bases, uint32_t *dev_mask, uint8_t *dev_qual, int64_t base_cap) {
+    if (!sh) return PPG_ARG_ERROR;
+    const bool off = !dev_seq_off && !dev_seq_len && !dev_bases && !dev_mask && !dev_qual && !rec_cap && !base_cap;
+    if (!off && !seq_args_ok(dev_seq_off, dev_seq_len, rec_cap, dev_bases, dev_mask, dev_qual, base_cap))
+        return PPG_ARG_ERROR;
+    sh->sp_off = dev_seq_off;
+    sh->sp_len = dev_seq_len;
+    sh->sp_bases = dev_bases;
+    sh->sp_mask = dev_mask;
+    sh->sp_qual = dev_qual;
+    sh->sp_rec_cap = rec_cap;
+    sh->sp_base_cap = base_cap;
+    sh->sp_written = 0;   // filled by the next run, not by an earlier one
+    return PPG_OK;
+}
+
+int ppg_shard_seqpack_ready(ppg_shard *sh, int64_t *total_bases) {
+    if (!sh) return PPG_ARG_ERROR;
+    if (!sh->sp_written) return 0;
+    if (total_bases) *total_bases = sh->sp_total;
+    return 1;
+}
+
+// Measurement hook of tools/seqpack_probe.py (not part of the ABI: no declaration in ppgpu.h).  On a
+// one-batch shard after its run, device time by hipEvents on the shard's stream, the median of reps
+// launches after one warm-up each, into ms[0..3]: layout totals + scan, seq_off / seq_len, the pack
+// (qualities when quality != 0), and ppg_pack_raw of the same batch (the text cursor's kernel, which
+// reads the same bytes and writes all of them); bytes[0..1]: the planes' and the raw text's sizes.
+int ppgx_seqpack_times(ppg_shard *sh, int quality, int reps, float *ms, int64_t *bytes) {
+    if (!sh || !sh->ran || sh->batches.size() != 1 || !ms || !bytes || reps < 1) return PPG_ARG_ERROR;
+    HIPCHK(hipSetDevice(sh->ctx->device));
+    hipStream_t s = shard_stream(sh);
+    int64_t total = 0;
+    if (int rc = shard_seq_layout(sh, 0, sh->n, sh->recs.p, &total)) return rc;
+    const int64_t nrec = sh->total_records;
+    std::vector<int64_t> raw_off((size_t)sh->n + 1, 0);
+    for (int32_t k = 0; k < sh->n; k++)
+        raw_off[(size_t)k + 1] = raw_off[(size_t)k] + (int64_t)sh->h_jobs[(size_t)k].raw_shift + (int64_t)sh->h_res[(size_t)k].produced;
+    DevBuf<int64_t> off, draw;
+    DevBuf<uint32_t> len, bases, mask;
+    DevBuf<uint8_t> qual, text;
+    HIPCHK(off.alloc((size_t)nrec + 1));
+    HIPCHK(len.alloc((size_t)nrec));
+    HIPCHK(bases.alloc((size_t)total / 16));
+    HIPCHK(mask.alloc((size_t)total / 32));
+    if (quality) HIPCHK(qual.alloc((size_t)total));
+    HIPCHK(text.alloc((size_t)raw_off[(size_t)sh->n]));
+    HIPCHK(draw.alloc(raw_off.size()));
+    HIPCHK(hipMemcpyAsync(draw.p, raw_off.data(), 8 * raw_off.size(), hipMemcpyHostToDevice, s));
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    HIPCHK(hipEventCreate(&e0));
+    HIPCHK(hipEventCreate(&e1));
+    int rc = PPG_OK;
+    for (int what = 0; what < 4 && rc == PPG_OK; what++) {
+        std::vector<float> t;
+        for (int r = 0; r <= reps && rc == PPG_OK; r++) {
+            hipError_t e = hipEventRecord(e0, s);
+            if (e == hipSuccess && what == 0) {
+                e = ppg_launch_seq_totals(s, sh->res.p, sh->info.p, sh->base.p, sh->recs.p, sh->sp_ctot.p, sh->n);
+                if (e == hipSuccess) e = ppg_launch_seq_scan(s, sh->sp_ctot.p, sh->sp_cbase.p, (uint64_t *)sh->sp_htot.p, sh->n);
+            } else if (e == hipSuccess && what == 1) {
+                e = ppg_launch_seq_offsets(s, sh->res.p, sh->info.p, sh->base.p, sh->recs.p, sh->sp_cbase.p, 0, off.p, len.p,
+                                           sh->n);
+            } else if (e == hipSuccess && what == 2) {
+                e = ppg_launch_seq_pack(s, sh->out.p, sh->jobs.p, sh->res.p, sh->offs.p, sh->oref.p, sh->info.p, sh->base.p,
+                                        sh->recs.p, sh->sp_cbase.p, off.p, len.p, 0, (uint64_t)total, bases.p, mask.p,
+                                        quality ? qual.p : nullptr, sh->n);
+            } else if (e == hipSuccess) {
+                e = ppg_launch_pack_raw(s, sh->out.p, sh->jobs.p, sh->res.p, sh->offs.p, sh->oref.p, draw.p, text.p, sh->n, 0);
+            }
+            if (e == hipSuccess) e = hipEventRecord(e1, s);
+            if (e == hipSuccess) e = hipEventSynchronize(e1);
+            float v = 0;
+            if (e == hipSuccess) e = hipEventElapsedTime(&v, e0, e1);
+            if (e != hipSuccess) rc = PPG_DEVICE_ERROR;
+            if (r) t.push_back(v);   // (r = 0 warms up)
+        }
+        if (rc == PPG_OK) {
+            std::sort(t.begin(), t.end());
+            ms[what] = t[t.size() / 2];
+        }
+    }
+    (void)hipEventDestroy(e0);
+    (void)hipEventDestroy(e1);
+    bytes[0] = total / 4 + total / 8 + (quality ? total : 0) + 12 * nrec + 8;
+    bytes[1] = raw_off[(size_t)sh->n];
+    return rc;
 }
 
 int ppg_shard_record_base(ppg_shard *sh, int64_t *base) {

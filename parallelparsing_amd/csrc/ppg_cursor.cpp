@@ -20,6 +20,12 @@
 // (ppg_index_build_gpu_side) splits a batch's chunks into several waves when the batch is too
 // small to fill the GPU by itself.
 //
+// A packed cursor (ppg_cursor_open_packed) relieves that bound instead of chasing it: after the
+// decode it lays out and packs the batch's reads on the device (ppg_seqpack.hip) and only the planes
+// -- 2-bit bases, the N mask, seq_off / seq_len and, when asked for, the qualities -- cross PCIe:
+// derived from the formats, ~232 B per 150 bp record with qualities and ~72 B without, against
+// 401 B of text + descriptors.  ppg_pack_raw, the text copy and the descriptor copy are skipped.
+//
 // A batch stays valid until the next ppg_cursor_next call (the reference's records are likewise
 // invalid after the next MoveNext, BatchedFASTQ.cs:56 / SURVEY Q9).  Order is canonical (chunk 0's
 // records, then chunk 1's, ...), not the reference's interleaving.
@@ -50,6 +56,12 @@ struct Slot {
     DevBuf<int64_t> draw_off;
     PinnedBuf desc;                     // 4 x u32 per record
     std::vector<int64_t> raw_off, rec_off;
+    // a packed cursor's batch (ppg_cursor_open_packed): its planes on the device, then pinned
+    DevBuf<int64_t> dseq_off;
+    DevBuf<uint32_t> dseq_len, dbases, dmask;
+    DevBuf<uint8_t> dqual;
+    PinnedBuf hseq_off, hseq_len, hbases, hmask, hqual;
+    int64_t seq_total = 0;              // the batch's padded bases
     int32_t b0 = 0, b1 = 0;             // chunks [b0, b1) relative to the cursor's first
     int64_t nrec = 0;
     int rc = PPG_OK;
@@ -87,6 +99,10 @@ struct ppg_cursor {
     // (decode 90 -> 250-440 ms with a pack in flight, any grid size, r03), so it loses
     int pack = 1;
     int pack_blocks = 256;              // pack = 2: workgroups of the pack kernels (PPG_CURSOR_PACK_BLOCKS)
+    bool packed = false;                // batches carry packed reads instead of text + descriptors
+    bool quality = false;               // ... with the quality plane
+    const Slot *cur = nullptr;          // the batch handed out last (the packed accessors read it)
+    int64_t pk_rec = 0, pk_bases = 0;   // packed slots: records / padded bases they are sized for at open
     bool verbose = false;               // PPG_CURSOR_VERBOSE: per-batch stage times on stderr
     std::chrono::steady_clock::time_point t_open = std::chrono::steady_clock::now();
     size_t next = 0;                    // next batch to hand out
@@ -150,8 +166,18 @@ struct ppg_cursor {
         // descriptors) and on the device (the same + the shard's output, census and records):
         // fewer slots (not below 2) when they would take more than half the available host memory
         // or 80% of the free device memory (at 4 GiB batches, 5 slots are ~28 GB pinned)
-        const double host_slot = (double)cmax + (double)rmax * 1.125;
-        const double dev_slot = (double)cmax + (double)rmax * (pack == 1 ? 2.4 : 1.4);
+        // A packed slot is sized from a bound on well-formed text: a record of L bases has a quality
+        // line as long, so its text is at least 2 L + 6 bytes and its padded bases P <= L + 31 are at
+        // most half its text + 31; with records of 64 B or more on average (36 bp reads are ~100 B)
+        // that is rmax / 64 records and rmax / 2 + 31 * rmax / 64 < rmax bases.  Records without a
+        // quality line (P up to text + 27) or shorter than 64 B can exceed it: such a batch grows
+        // its slot (grow_packed), as the descriptor buffer grows.
+        pk_rec = rmax / 64 + 4096;
+        pk_bases = (rmax / 2 + 31 * pk_rec + 31) / 32 * 32;
+        const double pk_bytes = (double)pk_bases * (quality ? 1.375 : 0.375) + 12.0 * (double)pk_rec;
+        const double host_slot = (double)cmax + (packed ? pk_bytes : (double)rmax * 1.125);
+        const double dev_slot = (double)cmax + (packed ? (double)rmax * 1.4 + pk_bytes
+                                                       : (double)rmax * (pack == 1 ? 2.4 : 1.4));
         size_t dfree = 0, dtotal = 0;
         const double havail = host_mem_available();
         if (hipMemGetInfo(&dfree, &dtotal) != hipSuccess) dfree = 0;
@@ -162,12 +188,35 @@ struct ppg_cursor {
             Slot &s = slot[q];
             HIPCHK(s.pcomp.alloc((size_t)cmax));
             HIPCHK(s.dcomp.alloc((size_t)cmax + 64));
-            HIPCHK(s.text.alloc((size_t)rmax));
-            if (pack) HIPCHK(s.draw_off.alloc((size_t)max_chunks + 1));
-            if (pack == 1) HIPCHK(s.dtext.alloc((size_t)rmax));
-            // descriptors: 16 B per record, for records of >= 128 B on average (grown only beyond)
-            HIPCHK(s.desc.alloc((size_t)(rmax / 8 + 4096)));
+            if (packed) {
+                if (int rc = grow_packed(s, pk_rec, pk_bases)) return rc;
+                if (int rc = shard_seq_reserve(&s.sh, max_chunks)) return rc;
+            } else {
+                HIPCHK(s.text.alloc((size_t)rmax));
+                if (pack) HIPCHK(s.draw_off.alloc((size_t)max_chunks + 1));
+                if (pack == 1) HIPCHK(s.dtext.alloc((size_t)rmax));
+                // descriptors: 16 B per record, for records of >= 128 B on average (grown only beyond)
+                HIPCHK(s.desc.alloc((size_t)(rmax / 8 + 4096)));
+            }
             if (int rc = shard_reserve(&s.sh, ix, first, batches, split)) return rc;
+        }
+        return PPG_OK;
+    }
+
+    // a packed slot's planes for nrec records and `bases` padded bases (a multiple of 32); buffers
+    // that are large enough stay
+    int grow_packed(Slot &s, int64_t nrec, int64_t bases) {
+        HIPCHK(s.dseq_off.alloc((size_t)nrec + 1));
+        HIPCHK(s.dseq_len.alloc((size_t)nrec));
+        HIPCHK(s.dbases.alloc((size_t)bases / 16));
+        HIPCHK(s.dmask.alloc((size_t)bases / 32));
+        HIPCHK(s.hseq_off.alloc(8 * ((size_t)nrec + 1)));
+        HIPCHK(s.hseq_len.alloc(4 * (size_t)nrec));
+        HIPCHK(s.hbases.alloc((size_t)bases / 4));
+        HIPCHK(s.hmask.alloc((size_t)bases / 8));
+        if (quality) {
+            HIPCHK(s.dqual.alloc((size_t)bases));
+            HIPCHK(s.hqual.alloc((size_t)bases));
         }
         return PPG_OK;
     }
@@ -212,8 +261,39 @@ struct ppg_cursor {
         for (int32_t k = 0; k < m; k++)
             s.raw_off[(size_t)k + 1] = s.raw_off[(size_t)k] + (int64_t)P[(size_t)a + k].offset.size() +
                                        (int64_t)s.sh.h_res[(size_t)k].produced;
-        if ((size_t)s.raw_off[(size_t)m] > s.text.n) return PPG_BUF_ERROR;   // produced <= Output span: never
+        if (!packed && (size_t)s.raw_off[(size_t)m] > s.text.n) return PPG_BUF_ERROR;  // produced <= Output span: never
         s.nrec = s.sh.total_records;
+        if (packed) {
+            // layout and pack while the batch is resident; only the planes cross PCIe
+            if (int rc = shard_seq_layout(&s.sh, 0, m, s.sh.recs.p, &s.seq_total)) return rc;
+            if ((size_t)s.nrec > s.dseq_len.n || (size_t)s.seq_total / 32 > s.dmask.n)
+                if (int rc = grow_packed(s, s.nrec + s.nrec / 4, (s.seq_total + s.seq_total / 4 + 31) / 32 * 32)) return rc;
+            if (int rc = shard_seq_pack(&s.sh, 0, m, s.sh.recs.p, 0, s.seq_total, s.dseq_off.p, s.dseq_len.p, s.dbases.p,
+                                        s.dmask.p, quality ? s.dqual.p : nullptr))
+                return rc;
+            stage_wait(i, kHost);
+            const double th = ms();
+            const size_t nb = (size_t)s.seq_total;
+            HIPCHK(hipMemcpyAsync(s.hseq_off.p, s.dseq_off.p, 8 * ((size_t)s.nrec + 1), hipMemcpyDeviceToHost, st));
+            if (s.nrec) HIPCHK(hipMemcpyAsync(s.hseq_len.p, s.dseq_len.p, 4 * (size_t)s.nrec, hipMemcpyDeviceToHost, st));
+            if (nb) {
+                HIPCHK(hipMemcpyAsync(s.hbases.p, s.dbases.p, nb / 4, hipMemcpyDeviceToHost, st));
+                HIPCHK(hipMemcpyAsync(s.hmask.p, s.dmask.p, nb / 8, hipMemcpyDeviceToHost, st));
+                if (quality) HIPCHK(hipMemcpyAsync(s.hqual.p, s.dqual.p, nb, hipMemcpyDeviceToHost, st));
+            }
+            HIPCHK(hipStreamSynchronize(st));
+            stage_done(i, kHost);
+            if (verbose)
+                fprintf(stderr, "[cursor] packed batch %zu: %d chunks, started at %.1f ms: read wait %.1f, read %.1f, "
+                                "H2D+prepare %.1f, decode %.1f (kernels %.1f), layout+pack queued %.1f, host wait + to host "
+                                "%.1f, total %.1f ms\n", i, m,
+                        std::chrono::duration<double, std::milli>(t0 - t_open).count(), tw, tr - tw, tp - tr, td - tp,
+                        (double)kms, th - td, ms() - th, ms());
+            s.rec_off.assign((size_t)m + 1, 0);
+            for (int32_t k = 0; k < m; k++)
+                s.rec_off[(size_t)k + 1] = s.sh.h_base[(size_t)k] + (int64_t)s.sh.h_info[(size_t)k].records;
+            return PPG_OK;
+        }
         if ((size_t)(16 * s.nrec) > s.desc.n) HIPCHK(s.desc.alloc((size_t)(16 * s.nrec + (16 * s.nrec) / 4)));
         stage_wait(i, kHost);
         const double th = ms();
@@ -268,8 +348,8 @@ struct ppg_cursor {
 
 extern "C" {
 
-int ppg_cursor_open(ppg_ctx *ctx, const ppg_index *ix, const char *gz_path, int32_t first, int32_t n,
-                    int64_t batch_bytes, int threads, ppg_cursor **out) {
+static int cursor_open(ppg_ctx *ctx, const ppg_index *ix, const char *gz_path, int32_t first, int32_t n,
+                       int64_t batch_bytes, int threads, bool packed, bool quality, ppg_cursor **out) {
     if (!ctx || !ix || !gz_path || !out || first < 0 || n < 0 || (size_t)first + (size_t)n + 1 > ix->pts.size())
         return PPG_ARG_ERROR;
     if (int v = ppg_index_validate(ix, first, n)) return v;
@@ -281,6 +361,8 @@ int ppg_cursor_open(ppg_ctx *ctx, const ppg_index *ix, const char *gz_path, int3
     c->first = first;
     c->n = n;
     c->threads = threads > 0 ? threads : 8;
+    c->packed = packed;
+    c->quality = quality;
     if (const char *e = getenv("PPG_CURSOR_SLOTS")) c->nslots = std::min(kMaxSlots, std::max(2, atoi(e)));
     if (const char *e = getenv("PPG_CURSOR_PACK")) c->pack = std::min(2, std::max(0, atoi(e)));
     if (const char *e = getenv("PPG_CURSOR_PACK_BLOCKS")) c->pack_blocks = std::max(4, atoi(e));
@@ -320,6 +402,37 @@ int ppg_cursor_open(ppg_ctx *ctx, const ppg_index *ix, const char *gz_path, int3
     return PPG_OK;
 }
 
+int ppg_cursor_open(ppg_ctx *ctx, const ppg_index *ix, const char *gz_path, int32_t first, int32_t n,
+                    int64_t batch_bytes, int threads, ppg_cursor **out) {
+    return cursor_open(ctx, ix, gz_path, first, n, batch_bytes, threads, false, false, out);
+}
+
+int ppg_cursor_open_packed(ppg_ctx *ctx, const ppg_index *ix, const char *gz_path, int32_t first, int32_t n,
+                           int64_t batch_bytes, int threads, int32_t planes, ppg_cursor **out) {
+    if (planes & ~1) return PPG_ARG_ERROR;
+    return cursor_open(ctx, ix, gz_path, first, n, batch_bytes, threads, true, (planes & 1) != 0, out);
+}
+
+int ppg_cursor_packed(const ppg_cursor *c, uint32_t **bases, uint32_t **mask, uint8_t **qual, uint32_t **seq_len,
+                      int64_t *total_bases) {
+    if (!c || !c->packed || !c->cur) return PPG_ARG_ERROR;
+    const Slot &s = *c->cur;
+    if (bases) *bases = (uint32_t *)s.hbases.p;
+    if (mask) *mask = (uint32_t *)s.hmask.p;
+    if (qual) *qual = c->quality ? s.hqual.p : nullptr;
+    if (seq_len) *seq_len = (uint32_t *)s.hseq_len.p;
+    if (total_bases) *total_bases = s.seq_total;
+    return PPG_OK;
+}
+
+int ppg_cursor_packed_offsets(const ppg_cursor *c, int64_t *seq_off, int64_t cap) {
+    if (!c || !c->packed || !c->cur || !seq_off) return PPG_ARG_ERROR;
+    const Slot &s = *c->cur;
+    if (cap < s.nrec + 1) return PPG_BUF_ERROR;
+    memcpy(seq_off, s.hseq_off.p, 8 * ((size_t)s.nrec + 1));
+    return PPG_OK;
+}
+
 int ppg_cursor_next(ppg_cursor *c, ppg_batch *b) {
     if (!c || !b) return PPG_ARG_ERROR;
     if (c->next >= c->batches.size()) return PPG_STREAM_END;
@@ -337,11 +450,12 @@ int ppg_cursor_next(ppg_cursor *c, ppg_batch *b) {
     b->nchunks = s.b1 - s.b0;
     b->record_base = c->record_base;
     b->nrecords = s.nrec;
-    b->text = s.text.p;
+    b->text = c->packed ? nullptr : s.text.p;
     b->raw_off = s.raw_off.data();
-    b->desc = (const uint32_t *)s.desc.p;
+    b->desc = c->packed ? nullptr : (const uint32_t *)s.desc.p;
     b->rec_off = s.rec_off.data();
     c->record_base += s.nrec;
+    c->cur = &s;
     c->next++;
     return PPG_OK;
 }

@@ -183,6 +183,16 @@ struct ppg_shard {
     int64_t *keys_dev = nullptr;
     int64_t keys_cap = 0;
     int keys_written = 0;   // the last successful run filled keys_dev (set by shard_run)
+    // ppg_shard_set_seqpack: every batch also packs its reads into these planes (ppg_seqpack.hip),
+    // records at their shard record number, bases continuing from the batches before (sp_total)
+    int64_t *sp_off = nullptr;
+    uint32_t *sp_len = nullptr, *sp_bases = nullptr, *sp_mask = nullptr;
+    uint8_t *sp_qual = nullptr;
+    int64_t sp_rec_cap = 0, sp_base_cap = 0;
+    int64_t sp_total = 0;   // padded bases of the run's batches so far
+    int sp_written = 0;     // the last successful run filled the planes (set by shard_run)
+    DevBuf<uint64_t> sp_ctot, sp_cbase;   // per-chunk padded bases and their scan (n + 1 entries)
+    PinnedBuf sp_htot;                    // the scan's total, stored by the kernel
     // split chunks (ppg_shard_set_split): the inflate launch runs sub-jobs, ppg_split_merge folds
     // them back into per-chunk results and census regions
     int32_t nsub = 0;                            // side points in use (0: one wave per chunk)
@@ -226,6 +236,14 @@ int shard_set_split_impl(ppg_shard *sh, int32_t nsub, const int64_t *bit, const 
 int shard_reserve(ppg_shard *sh, const ppg_index *ix, int32_t first,
                   const std::vector<std::pair<int32_t, int32_t>> &ranges, bool split);
 bool pread_parallel(int fd, uint8_t *dst, int64_t off, int64_t len, int threads);
+// packed reads of chunks [b0, b1) of one resident batch (recs: the batch's first descriptor).
+// layout: per-chunk padded bases, their scan and the batch's total (blocks on the shard's stream);
+// pack: seq_off / seq_len of the batch's records (pointers at its first record; bases from carry)
+// and the planes, queued on the stream after a layout of the same chunks.
+int shard_seq_reserve(ppg_shard *sh, int64_t nchunks);
+int shard_seq_layout(ppg_shard *sh, int32_t b0, int32_t b1, const uint32_t *recs, int64_t *total);
+int shard_seq_pack(ppg_shard *sh, int32_t b0, int32_t b1, const uint32_t *recs, int64_t carry, int64_t total,
+                   int64_t *seq_off, uint32_t *seq_len, uint32_t *bases, uint32_t *mask, uint8_t *qual);
 
 // collectives of a ppg_comm beyond the count gather (ppg_comm.cpp), used by ppg_pairs.hip
 int comm_size(const ppg_comm *c, int32_t *rank, int32_t *nranks);
