@@ -169,12 +169,30 @@ class Device:
         check(lib.ppg_open(int(device), C.byref(h)), f"ppg_open({device})")
         self._h = h
         self.device = device
+        self._users = 0          # live Shards / Cursors: their ppg_*_free reads this ctx
+        self._dropped = False
 
     def __del__(self):
+        # The cyclic collector finalises a Device and the Shards that refer to it in any order (a
+        # traceback that holds them is such a cycle), and ppg_shard_free / ppg_cursor_close read the
+        # ctx: the ctx is closed by whichever goes last.
+        self._dropped = True
+        if getattr(self, "_users", 0) == 0:
+            self._close()
+
+    def _close(self):
         h = getattr(self, "_h", None)
         if h is not None and h.value and lib is not None:   # (lib is None at interpreter exit)
             lib.ppg_close(h)
             self._h = None
+
+    def _retain(self):
+        self._users += 1
+
+    def _release(self):
+        self._users -= 1
+        if self._users == 0 and self._dropped:
+            self._close()
 
     @property
     def handle(self):
@@ -561,12 +579,14 @@ class Shard:
         check(lib.ppg_shard_create(self.dev.handle, index.handle, first, n, C.c_void_p(ptr), length,
                                    1 if comp_on_device else 0, int(out_capacity), C.byref(h)), "ppg_shard_create")
         self._h = h
+        self.dev._retain()
 
     def __del__(self):
         h = getattr(self, "_h", None)
         if h is not None and h.value and lib is not None:   # (lib is None at interpreter exit)
             lib.ppg_shard_free(h)
             self._h = None
+            self.dev._release()
 
     @property
     def handle(self):
@@ -873,6 +893,7 @@ class Cursor:
             check(lib.ppg_cursor_open(self.dev.handle, index.handle, os.fsencode(gzip_path), int(first), int(n),
                                       int(batch_bytes), int(threads), C.byref(h)), "ppg_cursor_open")
         self._h = h
+        self.dev._retain()
 
     def __del__(self):
         self.close()
@@ -882,6 +903,7 @@ class Cursor:
         if h is not None and h.value:
             lib.ppg_cursor_close(h)
             self._h = None
+            self.dev._release()
 
     @property
     def batches(self):

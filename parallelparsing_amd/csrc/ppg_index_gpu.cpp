@@ -286,6 +286,38 @@ struct Builder {
 
 }  // namespace
 
+// zlib's "invalid distance too far back" at the start of the member: a match may not reach before
+// output byte 0.  Pass 1 decodes every piece over a symbolic history and piece 0's history resolves to
+// 32 KiB of zeros, so the block-parallel decode would take such a member for valid text (and its CRC
+// can be written to fit).  Only a token that starts in the first 32 KiB of output can reach that far:
+// that prefix is inflated here on the host, by zlib without a dictionary, as the serial CreateIndex
+// does (~0.1 ms).  head: the file's first head_n bytes on the host; when they end before 32 KiB of
+// output (empty blocks by the thousand), a longer prefix is fetched from dcomp, the member in HBM.
+static int check_member_start(const uint8_t *dcomp, int64_t len, const uint8_t *head, int64_t head_n, int64_t hl) {
+    std::vector<uint8_t> more, text(kWin);
+    const uint8_t *in = head;
+    int64_t n = head_n;
+    for (;;) {
+        z_stream zs;
+        memset(&zs, 0, sizeof zs);
+        if (inflateInit2(&zs, -15) != Z_OK) return PPG_MEM_ERROR;
+        zs.next_in = (Bytef *)(in + hl);
+        zs.avail_in = (uInt)(n - hl);
+        zs.next_out = text.data();
+        zs.avail_out = (uInt)kWin;
+        const int ret = inflate(&zs, Z_NO_FLUSH);
+        const bool full = zs.avail_out == 0;
+        inflateEnd(&zs);
+        if (ret == Z_DATA_ERROR || ret == Z_NEED_DICT) return PPG_DATA_ERROR;
+        if (ret == Z_MEM_ERROR) return PPG_MEM_ERROR;
+        if (ret == Z_STREAM_END || full || n >= len || n >= (1ll << 30)) return PPG_OK;
+        n = std::min<int64_t>(len, n * 8);
+        more.resize((size_t)n);
+        HIPCHK(hipMemcpy(more.data(), dcomp, (size_t)n, hipMemcpyDeviceToHost));
+        in = more.data();
+    }
+}
+
 static int build_index_gpu(ppg_ctx *ctx, const uint8_t *dcomp, int64_t len, const uint8_t *head, int64_t head_n,
                            const uint8_t trailer[8], uint32_t chunksize, int64_t piece_bytes, int64_t out_capacity,
                            int64_t side_bytes, ppg_index &ix) {
@@ -294,6 +326,7 @@ static int build_index_gpu(ppg_ctx *ctx, const uint8_t *dcomp, int64_t len, cons
     std::fill(stat, stat + kIxStats, 0.0);
     const int64_t hl = gzip_header_len(head, head_n);
     if (hl < 0 || len < hl + 8 + 1) return PPG_UNSUPPORTED;
+    if (int rc = check_member_start(dcomp, len, head, head_n, hl)) return rc;
     Builder B;
     B.ctx = ctx;
     B.s = ctx->stream;

@@ -628,6 +628,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_num_sgpr(80), amdgpu_wave
     uint32_t fl_done = 0;                                    // flushed up to this position
     uint32_t fl_next = UNIT - (uint32_t)(out_off % UNIT);   // next global UNIT boundary
     int status = ST_OK, flags = 0, last = 0, in_block = 0;
+    int mid_stored = 0;   // the output limit fell inside a stored block
     Canon clit = {0, 0, 0}, cdst = {0, 0, 0};   // per-lane canonical codes of the current block
     // flush of chunk positions [lo, hi) (never across a UNIT boundary except the plain case)
 #ifdef PPG_IX_STATS
@@ -715,7 +716,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_num_sgpr(80), amdgpu_wave
                 }
             }
             rd_seek(r, S.stream, (bytepos + copied) * 8, lane);
-            if (copied < slen) break;   // output full mid-block (zlib stops at avail_out == 0)
+            if (copied < slen) { mid_stored = 1; break; }   // output full mid-block (zlib stops at avail_out == 0)
             in_block = 0;
             if constexpr (IX) {
                 if (!block_end((bytepos + copied) * 8)) break;
@@ -1312,6 +1313,15 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_num_sgpr(80), amdgpu_wave
         rd_refill(r, S.stream, lane);
         if (canon_decode(r, clit, lit_sorted, lane) == 256) end_bit = rd_pos(r);
         else flags |= PPG_FLAG_NO_EOB;
+    }
+    // zlib does not stop at the end-of-block either: the inflate() call that writes the chunk's last
+    // byte goes on to the next block's three header bits when the slice still holds them (to.Bits >= 3),
+    // and block type 3 there is this chunk's DATA_ERROR (inflate.c TYPEDO; no longer header field fits
+    // into what is left of the slice's last byte).  Once per chunk, after the last round.
+    if (!IX && status == ST_OK && pos == len && !last && !mid_stored && !(flags & PPG_FLAG_NO_EOB) &&
+        end_bit + 3u <= bit_limit) {
+        rd_refill(r, S.stream, lane);
+        if ((br_take(r, 3) >> 1) == 3u) status = ST_DATA_ERROR;
     }
 #ifdef PPG_STATS
     if (!IX && lane == 0 && k < 4)
