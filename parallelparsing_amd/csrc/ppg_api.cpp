@@ -30,52 +30,9 @@
 #include "../../include/ppgpu.h"
 #include "ppg_device.h"
 #include "ppg_host.h"
+#include "ppg_launch.h"
 
-// launchers (ppg_inflate.hip, ppg_parse.hip)
-size_t ppg_inflate_lds_bytes(int ring_bits, int lit_bits);
-hipError_t ppg_launch_inflate(hipStream_t s, int ring_bits, int lit_bits, const uint32_t *comp, uint64_t nwords,
-                              const PpgInflateJob *jobs, const uint8_t *dicts, uint8_t *out, PpgInflateResult *res,
-                              int njobs, uint32_t *nls);
-hipError_t ppg_launch_total_to_host(hipStream_t s, const uint64_t *total, uint64_t *host);
-hipError_t ppg_launch_parse_count(hipStream_t s, const uint8_t *out, const PpgInflateJob *jobs,
-                                  const PpgInflateResult *ires, const uint8_t *offs, const PpgOffsetRef *oref,
-                                  PpgParseInfo *info, uint64_t *base, uint64_t *total, int n, const uint32_t *nls);
-hipError_t ppg_launch_materialize(hipStream_t s, const uint16_t *sym, const uint8_t *wins, const PpgMatInfo *mi,
-                                  const PpgInflateJob *jobs, uint8_t *out, PpgInflateResult *res, int njobs,
-                                  uint32_t *nls);
-hipError_t ppg_launch_split_merge(hipStream_t s, const PpgInflateJob *sjobs, const PpgInflateResult *sres,
-                                  const uint32_t *inv, const uint32_t *sidx, const uint32_t *snls,
-                                  const PpgInflateJob *jobs, PpgInflateResult *res, uint32_t *nls, int n);
-hipError_t ppg_launch_parse_emit(hipStream_t s, const uint8_t *out, const PpgInflateJob *jobs,
-                                 const PpgInflateResult *ires, const uint8_t *offs, const PpgOffsetRef *oref,
-                                 PpgParseInfo *info, const uint64_t *base, const uint32_t *nls, uint32_t *recs,
-                                 uint64_t cap, int n);
-hipError_t ppg_launch_record_keys(hipStream_t s, const uint8_t *out, const PpgInflateJob *jobs,
-                                  const PpgInflateResult *ires, const uint8_t *offs, const PpgOffsetRef *oref,
-                                  const PpgParseInfo *info, const uint64_t *base, const uint32_t *recs, int64_t *keys,
-                                  int n);
-hipError_t ppg_launch_pack_raw(hipStream_t s, const uint8_t *out, const PpgInflateJob *jobs, const PpgInflateResult *ires,
-                               const uint8_t *offs, const PpgOffsetRef *oref, const int64_t *raw_off, uint8_t *dst,
-                               int n, int blocks);
-// launchers (ppg_seqpack.hip).  Weak references: libppgpu.so always links that object, but the
-// host-only sanitizer build (tests/native) links these translation units with the kernel objects of
-// inflate / parse / index alone; there the packed-read entry points fail with PPG_UNSUPPORTED
-// (seq_linked) instead of the link failing.  There is no other implementation to fall back to.
-#define PPG_WEAK __attribute__((weak))
-PPG_WEAK hipError_t ppg_launch_seq_totals(hipStream_t s, const PpgInflateResult *ires, const PpgParseInfo *info,
-                                          const uint64_t *base, const uint32_t *recs, uint64_t *ctot, int n);
-PPG_WEAK hipError_t ppg_launch_seq_scan(hipStream_t s, const uint64_t *ctot, uint64_t *cbase, uint64_t *host_total,
-                                        int n);
-PPG_WEAK hipError_t ppg_launch_seq_offsets(hipStream_t s, const PpgInflateResult *ires, const PpgParseInfo *info,
-                                           const uint64_t *base, const uint32_t *recs, const uint64_t *cbase,
-                                           int64_t carry, int64_t *seq_off, uint32_t *seq_len, int n);
-PPG_WEAK hipError_t ppg_launch_seq_pack(hipStream_t s, const uint8_t *out, const PpgInflateJob *jobs,
-                                        const PpgInflateResult *ires, const uint8_t *offs, const PpgOffsetRef *oref,
-                                        const PpgParseInfo *info, const uint64_t *base, const uint32_t *recs,
-                                        const uint64_t *cbase, const int64_t *seq_off, const uint32_t *seq_len,
-                                        int64_t carry, uint64_t total, uint32_t *bases, uint32_t *mask, uint8_t *qual,
-                                        int n);
-static bool seq_linked() {
+static bool seq_linked() {   // (weak references, ppg_launch.h: absent from the host-only sanitizer build)
     return ppg_launch_seq_totals && ppg_launch_seq_scan && ppg_launch_seq_offsets && ppg_launch_seq_pack;
 }
 

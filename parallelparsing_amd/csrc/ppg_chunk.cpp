@@ -20,40 +20,22 @@
 //
 // Chunks whose index carries side points (ppg_index_build_gpu_side) are decoded as one wave per
 // piece between their inner block starts (ppg_shard_set_split), exactly as DecompressAll does; the
-// others get theirs found on the GPU (find_side_points, find_mat below).
+// others get theirs found on the GPU (find_side_points, find_mat: ppg_find.cpp).
 #include "ppg_host.h"
+#include "ppg_find.h"
 #include <atomic>
-#include <chrono>
 #include <condition_variable>
 #include <deque>
 #include <mutex>
 #include <thread>
 #include <sys/mman.h>
 
-hipError_t ppg_launch_block_find(hipStream_t s, const uint32_t *comp, uint64_t nwords, const uint64_t *lo,
-                                 const uint64_t *hi, uint64_t *cand, int n, int sub);
-hipError_t ppg_launch_inflate_ix(hipStream_t s, const uint32_t *comp, uint64_t nwords, const PpgInflateJob *jobs,
-                                 const uint8_t *dicts, uint8_t *out, PpgInflateResult *res, PpgBlockEnd *blk,
-                                 int njobs);
-hipError_t ppg_launch_inflate_ixf(hipStream_t s, const uint32_t *comp, uint64_t nwords, const PpgInflateJob *jobs,
-                                  const uint8_t *dicts, uint8_t *out, PpgInflateResult *res, PpgBlockEnd *blk,
-                                  int njobs);
-hipError_t ppg_launch_gather(hipStream_t s, const uint8_t *out, const uint8_t *dicts, const PpgGather *g, uint8_t *dst,
-                             const uint8_t *ref, uint32_t *diff, int n);
-hipError_t ppg_launch_resolve_chains(hipStream_t s, const uint8_t *ta, const uint32_t *slots, const uint4 *chains,
-                                     int nchains, const uint8_t *windows, uint8_t *W);
-hipError_t ppg_launch_pick_windows(hipStream_t s, const uint8_t *src, const uint32_t *idx, int n, uint8_t *dst);
-
 namespace {
 
 constexpr int kChunkSlots = 4;             // launches in flight / results being copied out
-constexpr uint64_t kPieceRing = 65536;     // CreateIndex pass 1's symbolic output ring per piece (IX_RING_BYTES)
-// launches of up to this many chunks split them at their inner block starts found on the GPU: ~16
-// waves per chunk, so 4,096 chunks already hold ~8 generations of the GPU's 8,192 wave slots
-constexpr int kFindMaxChunks = 4096;
 constexpr size_t kSliceAlign = 64;   // each gathered slice starts on its own 64-B line
-// chunks per launch: the materialise path's limit (find_mat, kMatMaxChunks below), whose launch of
-// 256 warm chunks takes 41 ms against 63 ms for 258 on the two-decode path (r05g)
+// chunks per launch: the materialise path's limit (find_mat), whose launch of 256 warm chunks takes
+// 41 ms against 63 ms for 258 on the two-decode path (r05g); no launch is too large for the block search
 constexpr size_t kMaxBatch = 256;
 // a second launch starts while one is decoding only with this many requests queued: otherwise the
 // queue grows during the running launch and the next one takes all of it (r04: with two slots taken
@@ -90,13 +72,6 @@ struct ChunkReq {
     int64_t fin_len = 0;
     bool fin_nrec = false;
 };
-
-// grow a buffer to `need` elements, by at least half again its size (no reallocation per call)
-template <class B>
-hipError_t grow_buf(B &b, size_t need) {
-    if (b.p && b.n >= need) return hipSuccess;
-    return b.alloc(std::max(need, b.n + b.n / 2));
-}
 
 // memcpy of many (dst, src, len) spans: on the calling thread when small, else spread over up to
 // 8 threads in 1 MiB pieces -- a launch gathers up to 256 slices into the pinned staging buffer and
@@ -164,43 +139,6 @@ int result_spans(const ChunkReq &req, uint8_t *out, int64_t out_cap, uint32_t *r
     }
     return PPG_OK;
 }
-
-// grow a big scratch buffer of the block search; out of device memory (e.g. beside a resident
-// DecompressAll shard) is not a failure of the requests: the caller decodes them whole instead
-#define GROW_OR_SKIP(b, n)                                                                      \
-    do {                                                                                        \
-        const hipError_t grow_e = grow_buf(b, n);                                               \
-        if (grow_e == hipErrorOutOfMemory) {                                                    \
-            (void)hipGetLastError();                                                            \
-            fprintf(stderr, "ppgpu: block search scratch %s of %zu elements: out of device memory, " \
-                    "the launch's chunks decoded whole\n", #b, (size_t)(n));                   \
-            return PPG_MEM_ERROR;                                                               \
-        }                                                                                       \
-        if (grow_e != hipSuccess) {                                                             \
-            fprintf(stderr, "ppgpu: grow %s failed: %s\n", #b, hipGetErrorString(grow_e));     \
-            return PPG_DEVICE_ERROR;                                                            \
-        }                                                                                       \
-    } while (0)
-
-// waves per candidate range of the block search: enough for ~16,384 waves in all, two generations of
-// the GPU's wave slots (a lone chunk's 48 ranges are searched by 32 waves each; r05: at 4,096 waves a
-// launch of 256 chunks searched its 3,840 ranges with one wave each, 7.0 ms)
-int find_sub(int ranges) { return std::max(1, std::min(32, 16384 / std::max(1, ranges))); }
-
-// device scratch of find_side_points (grow only)
-struct FindScratch {
-    DevBuf<uint16_t> sym;                  // materialise path: every piece's pass-1 symbols, whole
-    DevBuf<PpgMatInfo> mi;                 // ... and each materialised piece's info
-    DevBuf<uint64_t> lo, hi, cand;
-    DevBuf<PpgInflateJob> jobs;
-    DevBuf<PpgInflateResult> res;
-    DevBuf<PpgBlockEnd> blk;
-    DevBuf<uint8_t> ring, ta, ident, W;
-    DevBuf<PpgGather> gat;
-    DevBuf<uint32_t> slots, pick;
-    DevBuf<uint4> chains;
-    DevBuf<uint8_t> packed;
-};
 
 struct ChunkSlot {
     hipStream_t s = nullptr;
@@ -296,535 +234,6 @@ bool side_points_inside(const ppg_index *ix, int32_t k) {
     return true;
 }
 
-// PPG_CHUNK_VERBOSE=1: a launch's phases (ms) on stderr -- where a lone chunk's latency goes
-struct PhaseClock {
-    bool on;
-    std::chrono::steady_clock::time_point t0, t;
-    char buf[512];
-    int n = 0;
-    PhaseClock() : on(getenv("PPG_CHUNK_VERBOSE") != nullptr) { t0 = t = std::chrono::steady_clock::now(); buf[0] = 0; }
-    void mark(const char *what, hipStream_t s = nullptr) {
-        if (!on) return;
-        if (s) (void)hipStreamSynchronize(s);
-        const auto now = std::chrono::steady_clock::now();
-        n += snprintf(buf + n, sizeof buf - (size_t)n, " %s %.3f", what,
-                      std::chrono::duration<double, std::milli>(now - t).count());
-        t = now;
-        if (n >= (int)sizeof buf) n = (int)sizeof buf - 1;
-    }
-    // (at: the launch's start, ms on the steady clock -- overlapping launches of several slots line up)
-    void dump(size_t reqs, int slot) {
-        if (on)
-            fprintf(stderr, "PPG_CHUNK launch of %zu: total %.3f ms: slot %d at %.3f:%s\n", reqs,
-                    std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(), slot,
-                    std::chrono::duration<double, std::milli>(t0.time_since_epoch()).count(), buf);
-    }
-};
-
-// Side points for chunks whose index has none (a .gzi carries only the Points): the inner deflate
-// block starts of each chunk found on the GPU the way the GPU CreateIndex finds them
-// (ppg_index_gpu.cpp) -- candidate dynamic-block headers every ~1/16 of the chunk's compressed bytes
-// (ppg_block_find_kernel), each piece but the last decoded with symbolic output until a block ends
-// at or past the next candidate (the inflate kernel's IX mode, the same kernels as CreateIndex pass
-// 1), the chain of block ends walked from the chunk's own Point (a block end that is not the next
-// candidate's start ends the chain there: that end is still a real block start), and the 32 KiB
-// history at every verified block start resolved from the pieces' symbolic tails starting from the
-// Point's window (ppg_resolve_*).  A lone chunk then decodes as ~16 waves instead of one: the
-// speculative pass costs about one piece's decode, the split decode another.  Coordinates: bits in
-// the launch's gathered comp buffer, outputs in the launch's output (the shard's virtual ones).
-struct FindChunk {
-    uint64_t bit0, bit1;                // compressed bits of the chunk: [from's start bit, slice end)
-    uint64_t bit_end;                   // to's block start (8 to.Input - to.Bits), or bit1 for the last chunk
-    int64_t out0;                       // the chunk's first output byte (launch coordinates)
-    int64_t len;                        // the chunk's output bytes
-    uint32_t win;                       // the Point's 32 KiB: window `win` of the shard's device dicts
-};
-
-int find_side_points(ChunkSlot &sl, const uint32_t *comp, uint64_t nwords, const uint8_t *dwin,
-                     const std::vector<FindChunk> &ch,
-                     std::vector<int64_t> &sbit, std::vector<int64_t> &sout, ByteVec &swin, int64_t &nsplit,
-                     PhaseClock &clk) {
-    hipStream_t s = sl.s;
-    FindScratch &F = sl.fs;
-    // candidates: the chunk cut into up to 16 pieces of >= 48 KiB of compressed bytes
-    std::vector<uint64_t> lo, hi;
-    std::vector<size_t> cfirst(ch.size() + 1, 0);
-    for (size_t c = 0; c < ch.size(); c++) {
-        const uint64_t span = ch[c].bit1 - ch[c].bit0;
-        const uint64_t pb = std::max<uint64_t>(8ull * 48 * 1024, span / 16);
-        for (uint64_t a = ch[c].bit0 + pb; a + 8ull * 1024 < ch[c].bit1; a += pb) {
-            lo.push_back(a);
-            hi.push_back(std::min(a + pb, ch[c].bit1));
-        }
-        cfirst[c + 1] = lo.size();
-    }
-    if (lo.empty()) return PPG_OK;
-    const size_t nc = lo.size();
-    HIPCHK(grow_buf(F.lo, nc));
-    HIPCHK(grow_buf(F.hi, nc));
-    HIPCHK(grow_buf(F.cand, nc));
-    HIPCHK(hipMemcpyAsync(F.lo.p, lo.data(), 8 * nc, hipMemcpyHostToDevice, s));
-    HIPCHK(hipMemcpyAsync(F.hi.p, hi.data(), 8 * nc, hipMemcpyHostToDevice, s));
-    HIPCHK(ppg_launch_block_find(s, comp, nwords, F.lo.p, F.hi.p, F.cand.p, (int)nc, find_sub((int)nc)));
-    std::vector<uint64_t> cand(nc);
-    HIPCHK(hipMemcpyAsync(cand.data(), F.cand.p, 8 * nc, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipStreamSynchronize(s));
-    clk.mark("f.cand");
-    // pieces: chunk c's Point, then its candidates; every piece but the last decoded to the next
-    struct Piece { size_t chunk; uint64_t start, stop; };
-    std::vector<Piece> pc;
-    std::vector<size_t> pfirst(ch.size() + 1, 0);
-    for (size_t c = 0; c < ch.size(); c++) {
-        std::vector<uint64_t> st{ch[c].bit0};
-        for (size_t k = cfirst[c]; k < cfirst[c + 1]; k++)
-            if (cand[k] != ~0ull && cand[k] > st.back()) st.push_back(cand[k]);
-        for (size_t j = 0; j + 1 < st.size(); j++) pc.push_back({c, st[j], st[j + 1]});
-        pfirst[c + 1] = pc.size();
-    }
-    const size_t np = pc.size();
-    if (!np) return PPG_OK;
-    std::vector<PpgInflateJob> jobs(np);
-    uint64_t nblk = 0;
-    for (size_t q = 0; q < np; q++) {
-        PpgInflateJob &J = jobs[q];
-        J = PpgInflateJob{};
-        J.bit_start = pc[q].start;
-        J.bit_limit = ch[pc[q].chunk].bit1;
-        J.out_off = (uint64_t)q * kPieceRing;
-        J.expect_end = ~0ull;
-        J.stop_bit = pc[q].stop;
-        J.blk_off = (uint32_t)nblk;
-        J.blk_cap = (uint32_t)((pc[q].stop - pc[q].start) / 8 / 2048 + 64);
-        nblk += J.blk_cap;
-    }
-    HIPCHK(grow_buf(F.jobs, np));
-    HIPCHK(grow_buf(F.res, np));
-    HIPCHK(grow_buf(F.blk, (size_t)nblk));
-    HIPCHK(grow_buf(F.ring, np * 2 * kPieceRing));
-    HIPCHK(grow_buf(F.ta, np * 2 * kWin));
-    if (!F.ident.p) {   // u16 0..32767: position p < 0 of a piece is history symbol 32768 + p
-        std::vector<uint16_t> id(kWin);
-        for (int i = 0; i < kWin; i++) id[(size_t)i] = (uint16_t)i;
-        HIPCHK(F.ident.alloc(2 * kWin));
-        HIPCHK(hipMemcpyAsync(F.ident.p, id.data(), 2 * kWin, hipMemcpyHostToDevice, s));
-    }
-    HIPCHK(hipMemcpyAsync(F.jobs.p, jobs.data(), sizeof(PpgInflateJob) * np, hipMemcpyHostToDevice, s));
-    HIPCHK(ppg_launch_inflate_ix(s, comp, nwords, F.jobs.p, F.ident.p, F.ring.p, F.res.p, F.blk.p, (int)np));
-    std::vector<PpgInflateResult> res(np);
-    std::vector<PpgBlockEnd> blk((size_t)nblk);
-    HIPCHK(hipMemcpyAsync(res.data(), F.res.p, sizeof(PpgInflateResult) * np, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipMemcpyAsync(blk.data(), F.blk.p, sizeof(PpgBlockEnd) * nblk, hipMemcpyDeviceToHost, s));
-    // the symbolic tails: the last 32 Ki symbols of each piece's ring, as two 32 KiB byte halves
-    std::vector<PpgGather> g(2 * np);
-    HIPCHK(hipStreamSynchronize(s));
-    clk.mark("f.pass1");
-    for (size_t q = 0; q < np; q++) {
-        const uint64_t endb = 2 * res[q].produced;
-        g[2 * q] = PpgGather{(uint64_t)q * 2 * kPieceRing, (uint64_t)kWin, endb - kWin, 2 * kPieceRing - 1, 0};
-        g[2 * q + 1] = PpgGather{(uint64_t)q * 2 * kPieceRing, (uint64_t)kWin, endb, 2 * kPieceRing - 1, 0};
-    }
-    HIPCHK(grow_buf(F.gat, 2 * np));
-    HIPCHK(hipMemcpyAsync(F.gat.p, g.data(), sizeof(PpgGather) * 2 * np, hipMemcpyHostToDevice, s));
-    HIPCHK(ppg_launch_gather(s, F.ring.p, F.ident.p, F.gat.p, F.ta.p, nullptr, nullptr, (int)(2 * np)));
-    // the chains: piece j of a chunk is followed when its last block end is piece j+1's start
-    std::vector<std::vector<uint32_t>> chain(ch.size());
-    // the side point of a chain end is the FIRST block end of its piece with the same output: a
-    // sync flush's empty stored block (pigz, Z_SYNC_FLUSH) ends at the same output as the block
-    // before it, and the split decode of the piece before a side point stops (pos == len, the
-    // end-of-block consumed) at that first end, not past the empty block (a side point there was
-    // a DATA_ERROR in ppg_split_merge).  An end that adds no output, or reaches the chunk's end,
-    // is walked through but gets no side point (keep = 0).
-    struct End { uint64_t bit, out; bool keep; };
-    std::vector<std::vector<End>> ends(ch.size());   // chunk-relative output
-    for (size_t c = 0; c < ch.size(); c++) {
-        uint64_t outc = 0, last_kept = 0;
-        for (size_t q = pfirst[c]; q < pfirst[c + 1]; q++) {
-            const PpgInflateResult &r = res[q];
-            const uint32_t nb = std::min(r.nblocks, jobs[q].blk_cap);
-            if (r.status != 0 || nb == 0 || r.last || (r.flags & (PPG_FLAG_BLK_FULL | PPG_FLAG_OVERRUN))) break;
-            const PpgBlockEnd *bl = blk.data() + jobs[q].blk_off;
-            const uint64_t E = bl[nb - 1].end_bit;
-            if (E >= ch[c].bit_end || bl[nb - 1].out_end != r.produced) break;
-            uint32_t f = nb - 1;
-            while (f > 0 && bl[f - 1].out_end == bl[nb - 1].out_end) f--;
-            outc += r.produced;
-            const bool keep = outc > last_kept && (int64_t)outc < ch[c].len;
-            if (keep) last_kept = outc;
-            chain[c].push_back((uint32_t)q);
-            ends[c].push_back(End{bl[f].end_bit, outc, keep});
-            if (q + 1 >= pfirst[c + 1] || pc[q + 1].start != E) break;   // the next candidate was false
-        }
-    }
-    // histories at the verified block ends, every chain in one launch: W[0] = the Point's window,
-    // W[j+1] = T_j(W[j]); the kept ones packed on the device and copied back at once
-    size_t wmax = 0;
-    for (size_t c = 0; c < ch.size(); c++) wmax = std::max(wmax, chain[c].size() + 1);
-    if (wmax < 2) return PPG_OK;
-    HIPCHK(grow_buf(F.W, ch.size() * wmax * kWin));
-    HIPCHK(grow_buf(F.slots, ch.size() * wmax));
-    std::vector<uint32_t> sl_all(ch.size() * wmax, 0);
-    std::vector<uint4> cs;
-    for (size_t c = 0; c < ch.size(); c++) {
-        if (chain[c].empty()) continue;
-        std::copy(chain[c].begin(), chain[c].end(), sl_all.begin() + (ptrdiff_t)(c * wmax));
-        cs.push_back(uint4{(uint32_t)(c * wmax), (uint32_t)chain[c].size() + 1, ch[c].win, 0});
-    }
-    HIPCHK(grow_buf(F.chains, cs.size()));
-    HIPCHK(hipMemcpyAsync(F.slots.p, sl_all.data(), 4 * sl_all.size(), hipMemcpyHostToDevice, s));
-    HIPCHK(hipMemcpyAsync(F.chains.p, cs.data(), sizeof(uint4) * cs.size(), hipMemcpyHostToDevice, s));
-    HIPCHK(ppg_launch_resolve_chains(s, F.ta.p, F.slots.p, F.chains.p, (int)cs.size(), dwin, F.W.p));
-    const size_t base = sbit.size();
-    std::vector<uint32_t> pick;
-    for (size_t c = 0; c < ch.size(); c++) {
-        bool any = false;
-        for (size_t j = 0; j < ends[c].size(); j++) {
-            const End &e = ends[c][j];
-            if (!e.keep) continue;
-            pick.push_back((uint32_t)(c * wmax + j + 1));   // W[j + 1]: the history at the end of chain piece j
-            sbit.push_back((int64_t)e.bit);
-            sout.push_back(ch[c].out0 + (int64_t)e.out);
-            any = true;
-        }
-        nsplit += any;
-    }
-    swin.resize((base + pick.size()) * kWin);
-    if (!pick.empty()) {
-        HIPCHK(grow_buf(F.pick, pick.size()));
-        HIPCHK(grow_buf(F.packed, pick.size() * kWin));
-        HIPCHK(hipMemcpyAsync(F.pick.p, pick.data(), 4 * pick.size(), hipMemcpyHostToDevice, s));
-        HIPCHK(ppg_launch_pick_windows(s, F.W.p, F.pick.p, (int)pick.size(), F.packed.p));
-        HIPCHK(hipMemcpyAsync(swin.data() + base * kWin, F.packed.p, pick.size() * kWin, hipMemcpyDeviceToHost, s));
-    }
-    HIPCHK(hipStreamSynchronize(s));
-    clk.mark("f.resolve");
-    return PPG_OK;
-}
-
-// ---- the materialise path: one symbolic decode per piece instead of two (r05) ----
-// A launch of at most kMatMaxChunks chunks of plain indexes (no side points of their own) splits
-// each chunk at the inner block starts found on the GPU as find_side_points does, but its pass 1
-// covers the WHOLE chunk -- the last piece too, up to the chunk's end -- and keeps every piece's
-// symbolic output whole (ppg_inflate_kernel IXF).  A chunk whose chain of block ends is verified
-// from its Point to its end gets its pieces' exact starting histories resolved from the symbolic
-// tails and is then written out from the symbols (ppg_materialize_kernel, with the fused newline
-// census) -- no second decode; any other chunk is decoded whole, one wave, in the same launch.
-// A lone 10,000-record chunk: find ~0.5 ms + one symbolic decode of a single deflate block (~4 ms)
-// + resolve + materialise, instead of that plus a second decode of the same block.
-constexpr int kMatMaxChunks = (int)kMaxBatch;
-constexpr uint64_t kMatRatio = 10;        // symbol capacity per compressed byte of a piece (FASTQ: ~4)
-// candidate ranges per chunk and their least compressed size: a zlib -6 FASTQ block is ~16 K symbols,
-// ~20 KB of gzip, so ranges of ~1/16 chunk (60 KB) held 2-3 block starts of which the finder keeps
-// the first, and the slowest piece was several blocks long.  r05 (tools/chunk_latency.py, one box):
-// 16 ranges / 48 KiB: T = 1 5.68 ms (pass 1 3.8); 24 / 32: 4.72; 32 / 24: 3.94 (2.36); 48 / 16:
-// 2.90 (1.60); 64 / 12: 2.85 (1.61) -- pieces of one block each from 48 on; a 256-chunk launch
-// ~45 ms at every setting (the search grows as pass 1 shrinks)
-constexpr uint64_t kMatRanges = 48;
-constexpr uint64_t kMatMinRange = 16 * 1024;
-
-struct MatPiece {
-    uint64_t start, stop;       // bits: piece start, the next piece's start (the chunk's end for the last)
-    uint64_t sym_off, cap;      // symbols
-};
-
-int find_mat(ChunkSlot &sl, const uint32_t *comp, uint64_t nwords, const uint8_t *dwin, const std::vector<FindChunk> &ch,
-             std::vector<uint8_t> &covered, std::vector<std::vector<PpgMatInfo>> &pmi,
-             std::vector<std::vector<int64_t>> &pbit, std::vector<std::vector<int64_t>> &pout, PhaseClock &clk) {
-    hipStream_t s = sl.s;
-    FindScratch &F = sl.fs;
-    covered.assign(ch.size(), 0);
-    pmi.assign(ch.size(), {});
-    pbit.assign(ch.size(), {});
-    pout.assign(ch.size(), {});
-    std::vector<uint64_t> lo, hi;
-    std::vector<size_t> cfirst(ch.size() + 1, 0);
-    for (size_t c = 0; c < ch.size(); c++) {
-        const uint64_t span = ch[c].bit1 - ch[c].bit0;
-        const uint64_t pb = std::max<uint64_t>(8ull * kMatMinRange, span / kMatRanges);
-        for (uint64_t a = ch[c].bit0 + pb; a + 8ull * 1024 < ch[c].bit1; a += pb) {
-            lo.push_back(a);
-            hi.push_back(std::min(a + pb, ch[c].bit1));
-        }
-        cfirst[c + 1] = lo.size();
-    }
-    const size_t nc = lo.size();
-    std::vector<uint64_t> cand(nc);
-    if (nc) {
-        HIPCHK(grow_buf(F.lo, nc));
-        HIPCHK(grow_buf(F.hi, nc));
-        HIPCHK(grow_buf(F.cand, nc));
-        HIPCHK(hipMemcpyAsync(F.lo.p, lo.data(), 8 * nc, hipMemcpyHostToDevice, s));
-        HIPCHK(hipMemcpyAsync(F.hi.p, hi.data(), 8 * nc, hipMemcpyHostToDevice, s));
-        HIPCHK(ppg_launch_block_find(s, comp, nwords, F.lo.p, F.hi.p, F.cand.p, (int)nc, find_sub((int)nc)));
-        HIPCHK(hipMemcpyAsync(cand.data(), F.cand.p, 8 * nc, hipMemcpyDeviceToHost, s));
-        HIPCHK(hipStreamSynchronize(s));
-    }
-    clk.mark("f.cand");
-    // pieces: the Point, the candidates, up to the chunk's end; symbol capacity by compressed size
-    std::vector<MatPiece> pc;
-    std::vector<size_t> pfirst(ch.size() + 1, 0);
-    uint64_t syms = 0;
-    for (size_t c = 0; c < ch.size(); c++) {
-        std::vector<uint64_t> st{ch[c].bit0};
-        for (size_t k = cfirst[c]; k < cfirst[c + 1]; k++)
-            if (cand[k] != ~0ull && cand[k] > st.back() && cand[k] < ch[c].bit_end) st.push_back(cand[k]);
-        st.push_back(ch[c].bit_end);
-        for (size_t j = 0; j + 1 < st.size(); j++) {
-            // (at least 192 Ki symbols, ~1.5 zlib -6 FASTQ blocks: a piece whose next candidate is false
-            // decodes on to the next real block end, a whole block past a stop that may be only a few
-            // KB away; a piece of a typical ~20 KB range gets its 10x anyway, so the floor costs little)
-            const uint64_t cap = std::max<uint64_t>(192 * 1024, kMatRatio * ((st[j + 1] - st[j]) / 8 + 64));
-            pc.push_back(MatPiece{st[j], st[j + 1], syms, cap});
-            syms += cap + 2048;   // flushes may run up to a unit past the capacity check
-        }
-        pfirst[c + 1] = pc.size();
-    }
-    const size_t np = pc.size();
-    if (!np) return PPG_OK;
-    // a repair piece per chunk at most (below): its symbols, block ends and job reserved up front
-    // (grow_buf does not keep contents, and a hipFree mid-launch waits for the whole device)
-    uint64_t maxcap = 0;
-    for (const MatPiece &m : pc) maxcap = std::max(maxcap, m.cap);
-    const size_t nrep_cap = ch.size();
-    const uint64_t rep_syms = std::max<uint64_t>(4 * (maxcap + 2048), syms / 16);
-    std::vector<PpgInflateJob> jobs(np);
-    uint64_t nblk = 0;
-    for (size_t q = 0; q < np; q++) {
-        PpgInflateJob &J = jobs[q];
-        J = PpgInflateJob{};
-        J.bit_start = pc[q].start;
-        J.bit_limit = std::max<uint64_t>(pc[q].stop, 0);
-        J.out_off = pc[q].sym_off;
-        J.out_len = pc[q].cap;
-        J.expect_end = ~0ull;
-        J.stop_bit = pc[q].stop;
-        J.blk_off = (uint32_t)nblk;
-        J.blk_cap = (uint32_t)((pc[q].stop - pc[q].start) / 8 / 2048 + 64);
-        nblk += J.blk_cap;
-    }
-    const uint64_t rep_blk = 64 * nrep_cap + rep_syms / (kMatRatio * 2048) + 64;
-    // the piece may read up to its chunk's slice end (the last block of a non-final piece ends past
-    // its stop when the next candidate was false)
-    for (size_t c = 0; c < ch.size(); c++)
-        for (size_t q = pfirst[c]; q < pfirst[c + 1]; q++) jobs[q].bit_limit = ch[c].bit1;
-    HIPCHK(grow_buf(F.jobs, np + nrep_cap));
-    HIPCHK(grow_buf(F.res, np + nrep_cap));
-    GROW_OR_SKIP(F.blk, (size_t)(nblk + rep_blk));
-    GROW_OR_SKIP(F.sym, (size_t)(syms + rep_syms) + 64);
-    GROW_OR_SKIP(F.ta, (np + nrep_cap) * 2 * kWin);
-    clk.mark("f.grow");
-    if (!F.ident.p) {   // u16 0..32767: position p < 0 of a piece is history symbol 32768 + p
-        std::vector<uint16_t> id(kWin);
-        for (int i = 0; i < kWin; i++) id[(size_t)i] = (uint16_t)i;
-        HIPCHK(F.ident.alloc(2 * kWin));
-        HIPCHK(hipMemcpyAsync(F.ident.p, id.data(), 2 * kWin, hipMemcpyHostToDevice, s));
-    }
-    HIPCHK(hipMemcpyAsync(F.jobs.p, jobs.data(), sizeof(PpgInflateJob) * np, hipMemcpyHostToDevice, s));
-    HIPCHK(ppg_launch_inflate_ixf(s, comp, nwords, F.jobs.p, F.ident.p, (uint8_t *)F.sym.p, F.res.p, F.blk.p, (int)np));
-    std::vector<PpgInflateResult> res(np);
-    std::vector<PpgBlockEnd> blk((size_t)nblk);
-    HIPCHK(hipMemcpyAsync(res.data(), F.res.p, sizeof(PpgInflateResult) * np, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipMemcpyAsync(blk.data(), F.blk.p, sizeof(PpgBlockEnd) * nblk, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipStreamSynchronize(s));
-    clk.mark("f.pass1");
-    // a chunk is covered when its pieces chain from its Point to its end: each piece's last block
-    // end is where the chain's next piece starts -- normally the next candidate; after a false
-    // candidate (its piece fails, or the piece before it decodes on to the next real block end) the
-    // first later piece that starts there, the false ones skipped (r05: ~0.6% of chunks at 48
-    // ranges fell back to a one-wave decode of ~45 ms) --, the chain's last piece ends exactly at
-    // the chunk's end (or with the final block, for the file's last chunk), and their outputs add up.
-    // Two more cases chain (r05: 2 chunks in 1,024 were still left to the one-wave decode):
-    //  - the real block start after a false candidate is no candidate at all (the finder keeps one
-    //    per range): a repair piece from that block end to the next good piece's start, decoded in
-    //    a second, small pass 1;
-    //  - an index's last chunk, whose end is known only as its slice's last byte (no R-E5 end check:
-    //    expect_end ~0): its last piece ends a block inside that byte, with every byte of the chunk,
-    //    and decodes on into a next block header the slice does not hold, failing -- the piece is
-    //    taken up to that block end (r05: index chunk 1023 of the bench's per-chunk legs).
-    std::vector<size_t> wbase(ch.size(), 0);
-    std::vector<std::vector<uint32_t>> chain(ch.size());
-    std::vector<uint64_t> E(np, 0);
-    std::vector<uint8_t> cut(np, 0);                      // last pieces taken up to a block end in the slice's last byte
-    std::vector<std::vector<uint32_t>> reps(ch.size());   // each chunk's repair pieces (indexes >= np)
-    struct Repair {
-        size_t c;
-        uint64_t start, stop;
-    };
-    std::vector<Repair> want;
-    // chunk c's chain; 0 when covered, else why not (PPG_CHUNK_VERBOSE)
-    auto walk = [&](size_t c, bool may_repair) -> int {
-        chain[c].clear();
-        uint64_t tot = 0;
-        size_t q = pfirst[c];
-        for (;;) {
-            PpgInflateResult &r = res[q];
-            const uint32_t nb = std::min(r.nblocks, jobs[q].blk_cap);
-            if (r.status != 0 && nb > 0 && ch[c].bit_end == ch[c].bit1) {   // an index's last chunk
-                const PpgBlockEnd &e = blk[jobs[q].blk_off + nb - 1];
-                if (e.end_bit <= ch[c].bit_end && ch[c].bit_end - e.end_bit < 8 &&
-                    tot + e.out_end == (uint64_t)ch[c].len && e.out_end <= jobs[q].out_len) {
-                    r.status = 0;
-                    r.flags = 0;
-                    r.produced = e.out_end;
-                    r.nblocks = nb;
-                    r.last = 0;
-                    cut[q] = 1;
-                }
-            }
-            if (r.status != 0 || nb == 0 || (r.flags & (PPG_FLAG_BLK_FULL | PPG_FLAG_OVERRUN)))
-                return r.status != 0 ? 1 : nb == 0 ? 2 : (r.flags & PPG_FLAG_BLK_FULL) ? 3 : 4;
-            const PpgBlockEnd &e = blk[jobs[q].blk_off + nb - 1];
-            if (e.out_end != r.produced) return 5;
-            E[q] = e.end_bit;
-            chain[c].push_back((uint32_t)q);
-            tot += r.produced;
-            if (e.end_bit == ch[c].bit_end || cut[q] || (r.last && ch[c].bit_end == ch[c].bit1))
-                return (int64_t)tot == ch[c].len ? 0 : 9;
-            if (r.last) return 6;
-            size_t nx = q < np ? q + 1 : pfirst[c];   // the piece that starts at this end
-            while (nx < pfirst[c + 1] && pc[nx].start < e.end_bit) nx++;
-            if (nx < pfirst[c + 1] && pc[nx].start == e.end_bit) {
-                q = nx;
-                continue;
-            }
-            size_t rq = ~(size_t)0;
-            for (uint32_t x : reps[c])
-                if (pc[x].start == e.end_bit) rq = x;
-            if (rq != ~(size_t)0) {
-                q = rq;
-                continue;
-            }
-            if (may_repair) {   // up to the next piece that decoded, or the chunk's end
-                while (nx < pfirst[c + 1] && res[nx].status != 0) nx++;
-                want.push_back(Repair{c, e.end_bit, nx < pfirst[c + 1] ? pc[nx].start : ch[c].bit_end});
-            }
-            return 7;
-        }
-    };
-    std::vector<int> why(ch.size(), 0);
-    for (size_t c = 0; c < ch.size(); c++) why[c] = walk(c, true);
-    if (!want.empty()) {   // the repair pass
-        uint64_t rs = syms, rb = nblk;
-        std::vector<size_t> rc;
-        for (const Repair &w : want) {
-            const uint64_t cap = std::max<uint64_t>(192 * 1024, kMatRatio * ((w.stop - w.start) / 8 + 64));
-            const uint32_t bc = (uint32_t)((w.stop - w.start) / 8 / 2048 + 64);
-            if (w.stop <= w.start || rs + cap + 2048 > syms + rep_syms || rb + bc > nblk + rep_blk) continue;
-            PpgInflateJob J{};
-            J.bit_start = w.start;
-            J.bit_limit = ch[w.c].bit1;
-            J.out_off = rs;
-            J.out_len = cap;
-            J.expect_end = ~0ull;
-            J.stop_bit = w.stop;
-            J.blk_off = (uint32_t)rb;
-            J.blk_cap = bc;
-            reps[w.c].push_back((uint32_t)pc.size());
-            pc.push_back(MatPiece{w.start, w.stop, rs, cap});
-            jobs.push_back(J);
-            rc.push_back(w.c);
-            rs += cap + 2048;
-            rb += bc;
-        }
-        const size_t nr = pc.size() - np;
-        if (nr) {
-            res.resize(np + nr);
-            blk.resize((size_t)rb);
-            E.resize(np + nr, 0);
-            cut.resize(np + nr, 0);
-            HIPCHK(hipMemcpyAsync(F.jobs.p + np, jobs.data() + np, sizeof(PpgInflateJob) * nr, hipMemcpyHostToDevice, s));
-            HIPCHK(ppg_launch_inflate_ixf(s, comp, nwords, F.jobs.p + np, F.ident.p, (uint8_t *)F.sym.p, F.res.p + np,
-                                          F.blk.p, (int)nr));
-            HIPCHK(hipMemcpyAsync(res.data() + np, F.res.p + np, sizeof(PpgInflateResult) * nr, hipMemcpyDeviceToHost, s));
-            HIPCHK(hipMemcpyAsync(blk.data() + nblk, F.blk.p + nblk, sizeof(PpgBlockEnd) * (rb - nblk),
-                                  hipMemcpyDeviceToHost, s));
-            HIPCHK(hipStreamSynchronize(s));
-            std::sort(rc.begin(), rc.end());
-            rc.erase(std::unique(rc.begin(), rc.end()), rc.end());
-            for (size_t c : rc) why[c] = walk(c, false);
-        }
-        clk.mark("f.repair");
-    }
-    const size_t nt = pc.size();
-    size_t nw = 0;
-    for (size_t c = 0; c < ch.size(); c++) {
-        const bool ok = why[c] == 0;
-        if (!ok && clk.on) {
-            fprintf(stderr, "PPG_CHUNK not covered: chunk %zu reason %d after %zu chained of %zu pieces\n", c, why[c],
-                    chain[c].size(), pfirst[c + 1] - pfirst[c]);
-            for (size_t x = pfirst[c]; x < pfirst[c + 1]; x++) {
-                const PpgInflateResult &r = res[x];
-                const uint32_t nb = std::min(r.nblocks, jobs[x].blk_cap);
-                fprintf(stderr, "  piece %zu bits [%llu,%llu) chunk [%llu,%llu) cap %llu: status %d flags %u produced %llu "
-                        "blocks %u last_end %llu\n", x - pfirst[c], (unsigned long long)pc[x].start,
-                        (unsigned long long)pc[x].stop, (unsigned long long)ch[c].bit0, (unsigned long long)ch[c].bit_end,
-                        (unsigned long long)pc[x].cap, (int)r.status, (unsigned)r.flags, (unsigned long long)r.produced, nb,
-                        nb ? (unsigned long long)blk[jobs[x].blk_off + nb - 1].end_bit : 0ull);
-            }
-        }
-        covered[c] = ok;
-        if (ok) {
-            wbase[c] = nw;
-            nw += chain[c].size();
-        }
-    }
-    if (!nw) return PPG_OK;
-    // symbolic tails (the last 32 Ki symbols of each piece, as two 32 KiB byte halves), then every
-    // covered chunk's starting histories: W[0] = the Point's window, W[j+1] = T_j(W[j])
-    std::vector<PpgGather> g(2 * nt);
-    for (size_t q = 0; q < nt; q++) {
-        const uint64_t endb = 2 * res[q].produced, base = 2 * pc[q].sym_off;
-        g[2 * q] = PpgGather{base, (uint64_t)kWin, endb - kWin, ~0ull, 0};
-        g[2 * q + 1] = PpgGather{base, (uint64_t)kWin, endb, ~0ull, 0};
-    }
-    HIPCHK(grow_buf(F.gat, 2 * nt));
-    HIPCHK(hipMemcpyAsync(F.gat.p, g.data(), sizeof(PpgGather) * 2 * nt, hipMemcpyHostToDevice, s));
-    HIPCHK(ppg_launch_gather(s, (const uint8_t *)F.sym.p, F.ident.p, F.gat.p, F.ta.p, nullptr, nullptr, (int)(2 * nt)));
-    GROW_OR_SKIP(F.W, nw * kWin);
-    HIPCHK(grow_buf(F.slots, nw));
-    std::vector<uint32_t> sl_all(nw, 0);
-    std::vector<uint4> cs;
-    for (size_t c = 0; c < ch.size(); c++) {
-        if (!covered[c]) continue;
-        std::copy(chain[c].begin(), chain[c].end(), sl_all.begin() + (ptrdiff_t)wbase[c]);
-        cs.push_back(uint4{(uint32_t)wbase[c], (uint32_t)chain[c].size(), ch[c].win, 0});
-    }
-    HIPCHK(grow_buf(F.chains, cs.size()));
-    HIPCHK(hipMemcpyAsync(F.slots.p, sl_all.data(), 4 * nw, hipMemcpyHostToDevice, s));
-    HIPCHK(hipMemcpyAsync(F.chains.p, cs.data(), sizeof(uint4) * cs.size(), hipMemcpyHostToDevice, s));
-    HIPCHK(ppg_launch_resolve_chains(s, F.ta.p, F.slots.p, F.chains.p, (int)cs.size(), dwin, F.W.p));
-    // the pieces' materialise info, side points at every later piece's start (launch coordinates)
-    for (size_t c = 0; c < ch.size(); c++) {
-        if (!covered[c]) continue;
-        uint64_t outc = 0, last_end = 0;
-        for (size_t j = 0; j < chain[c].size(); j++) {
-            const size_t q = chain[c][j];
-            last_end = E[q];
-            if (res[q].produced == 0) continue;   // an empty piece (a flush block) adds nothing
-            if (!pmi[c].empty()) {
-                pbit[c].push_back((int64_t)pc[q].start);
-                pout[c].push_back(ch[c].out0 + (int64_t)outc);
-            }
-            PpgMatInfo m{};
-            m.sym_off = pc[q].sym_off;
-            m.win_off = (wbase[c] + j) * (uint64_t)kWin;
-            m.nblocks = res[q].nblocks;
-            m.last = res[q].last;
-            m.prev = pmi[c].empty() ? 0x100u : 0x1FFu;   // 0x100: the chunk job's own (set below)
-            pmi[c].push_back(m);
-            outc += res[q].produced;
-        }
-        // each piece's end: where the next starts, the last one's block end
-        for (size_t i = 0; i < pmi[c].size(); i++)
-            pmi[c][i].end_bit = i + 1 < pmi[c].size() ? (uint64_t)pbit[c][i] : last_end;
-        if (pmi[c].empty()) covered[c] = 0;
-    }
-    // the H2D sources above (g, sl_all, cs) are pageable vectors that die here: wait for the copies
-    // (the phase clock syncs only when verbose)
-    HIPCHK(hipStreamSynchronize(s));
-    clk.mark("f.resolve", s);
-    return PPG_OK;
-}
-
 // One launch of the requests `batch` on slot `sl` (the caller holds the slot, not the lock).  Sets
 // every request's rc and, for a decoded chunk, where its bytes and descriptors sit in sl.res.
 int run_launch(ppg_ctx *ctx, ChunkService &svc, ChunkSlot &sl, std::vector<ChunkReq *> &batch) {
@@ -858,8 +267,8 @@ int run_launch(ppg_ctx *ctx, ChunkService &svc, ChunkSlot &sl, std::vector<Chunk
         comp_len += ((size_t)r->slice_len + kSliceAlign - 1) / kSliceAlign * kSliceAlign;
     }
     if (go.empty()) return PPG_OK;
-    // the materialise path (find_mat) takes launches of plain indexes up to kMatMaxChunks
-    bool mat = go.size() <= (size_t)kMatMaxChunks && !getenv("PPG_CHUNK_NO_FIND") && !getenv("PPG_CHUNK_NO_MAT");
+    // the materialise path (find_mat) takes launches of plain indexes (of any size: kMaxBatch above)
+    bool mat = !getenv("PPG_CHUNK_NO_FIND") && !getenv("PPG_CHUNK_NO_MAT");
     for (size_t i = 0; mat && i < go.size(); i++) mat = go[i]->ix->side_out.empty();
     {   // the shard's buffers with headroom, so launches of growing size do not reallocate each time
         size_t n = go.size(), offb = 0, tot = 0, nsub = 0, nwin = 0;
@@ -872,12 +281,12 @@ int run_launch(ppg_ctx *ctx, ChunkService &svc, ChunkSlot &sl, std::vector<Chunk
                                                                       std::upper_bound(O.begin(), O.end(), from.output));
             nsub += own;
             nwin += own;
-            if (O.empty() && n <= (size_t)kFindMaxChunks) {
-                nsub += kMatRanges;   // the block search's pieces at most
+            if (O.empty()) {
+                nsub += find_max_pieces();   // the block search's pieces at most
                 // side windows: the materialise path fills none (its pieces start from resolved
                 // histories, not dictionaries); find_side_points at most 15 per chunk (ADVICE r05:
                 // 48 windows of 32 KiB per chunk were reserved and never written, ~400 MB per slot)
-                if (!mat) nwin += 16;
+                if (!mat) nwin += find_max_side_windows();
             }
         }
         ppg_shard *sh = sl.sh;
@@ -915,17 +324,18 @@ int run_launch(ppg_ctx *ctx, ChunkService &svc, ChunkSlot &sl, std::vector<Chunk
     int rc = shard_prepare_specs(sh, spec.data(), (int32_t)go.size(), sl.comp.p, (int64_t)comp_len, 0, sl.s, nullptr);
     if (rc != PPG_OK) return rc;
     pc.mark("prepare");
-    if (mat) {   // the materialise path (find_mat above)
+    auto find_chunk = [&](size_t i) {   // chunk i of the launch, for the block search
+        const PpgInflateJob &J = sh->h_jobs[i];
+        return FindChunk{J.bit_start, J.bit_limit, J.expect_end != ~0ull ? J.expect_end : J.bit_limit, sh->h_pout[i],
+                         (int64_t)J.out_len, (uint32_t)i};
+    };
+    if (mat) {   // the materialise path (find_mat, ppg_find.cpp)
         std::vector<FindChunk> find;
-        for (size_t i = 0; i < go.size(); i++) {
-            const PpgInflateJob &J = sh->h_jobs[i];
-            find.push_back(FindChunk{J.bit_start, J.bit_limit, J.expect_end != ~0ull ? J.expect_end : J.bit_limit,
-                                     sh->h_pout[i], (int64_t)J.out_len, (uint32_t)i});
-        }
+        for (size_t i = 0; i < go.size(); i++) find.push_back(find_chunk(i));
         std::vector<uint8_t> covered;
         std::vector<std::vector<PpgMatInfo>> pmi;
         std::vector<std::vector<int64_t>> pbit, pout;
-        rc = find_mat(sl, (const uint32_t *)sl.comp.p, sh->nwords, sh->dicts.p, find, covered, pmi, pbit, pout, pc);
+        rc = find_mat(sl.s, sl.fs, (const uint32_t *)sl.comp.p, sh->nwords, sh->dicts.p, find, covered, pmi, pbit, pout, pc);
         if (rc == PPG_MEM_ERROR) {   // no room for the search's scratch: every chunk decoded whole
             covered.assign(go.size(), 0);
             rc = PPG_OK;
@@ -990,20 +400,19 @@ int run_launch(ppg_ctx *ctx, ChunkService &svc, ChunkSlot &sl, std::vector<Chunk
         std::vector<int64_t> sbit, sout;
         ByteVec swin;
         std::vector<FindChunk> find;
-        const bool findable = go.size() <= (size_t)kFindMaxChunks && !getenv("PPG_CHUNK_NO_FIND");
+        const bool findable = !getenv("PPG_CHUNK_NO_FIND");
         for (size_t i = 0; i < go.size(); i++) {
             if (!go[i]->ix->side_out.empty()) {
                 side_points_of(go[i]->ix, go[i]->k, sh->h_jobs[i].bit_start, sh->h_pout[i], sbit, sout, swin);
             } else if (findable && sh->h_jobs[i].out_len > 0) {
                 // sorted by output with the others: flush the found ones in launch order
-                const PpgInflateJob &J = sh->h_jobs[i];
-                find.push_back(FindChunk{J.bit_start, J.bit_limit, J.expect_end != ~0ull ? J.expect_end : J.bit_limit,
-                                         sh->h_pout[i], (int64_t)J.out_len, (uint32_t)i});
+                find.push_back(find_chunk(i));
             }
             if (!find.empty() && (i + 1 == go.size() || !go[i + 1]->ix->side_out.empty())) {
                 const size_t before = sbit.size();
                 int64_t nsplit = 0;
-                rc = find_side_points(sl, (const uint32_t *)sl.comp.p, sh->nwords, sh->dicts.p, find, sbit, sout, swin, nsplit, pc);
+                rc = find_side_points(sl.s, sl.fs, (const uint32_t *)sl.comp.p, sh->nwords, sh->dicts.p, find, sbit, sout, swin,
+                                      nsplit, pc);
                 if (rc != PPG_OK) return rc;
                 svc.found_chunks += nsplit;
                 svc.found_points += (int64_t)(sbit.size() - before);
@@ -1053,10 +462,6 @@ int run_launch(ppg_ctx *ctx, ChunkService &svc, ChunkSlot &sl, std::vector<Chunk
     return PPG_OK;
 }
 
-}  // namespace
-
-namespace {
-
 // a free slot (not decoding, nobody copying out of it), or -1
 int free_slot(const ChunkService &svc) {
     for (int i = 0; i < kChunkSlots; i++)
@@ -1068,8 +473,6 @@ int free_slot(const ChunkService &svc) {
 bool may_lead(const ChunkService &svc) {
     return !svc.pending.empty() && (svc.in_flight == 0 || svc.pending.size() >= kMinSecond);
 }
-
-using Svc = ChunkService;
 
 // async requests' results into the buffers given at submit, all at once (up to 8 threads); their
 // wait() then only hands back the status and counts
@@ -1094,7 +497,7 @@ void copier_loop(ChunkService *svc) {
         // (a launch still in flight may queue one more task: exit only after it)
         svc->cv.wait(lk, [&] { return !svc->copies.empty() || (svc->stop && svc->in_flight == 0); });
         if (svc->copies.empty()) return;
-        Svc::CopyTask t = std::move(svc->copies.front());
+        ChunkService::CopyTask t = std::move(svc->copies.front());
         svc->copies.pop_front();
         lk.unlock();
         PhaseClock clk;
@@ -1140,7 +543,7 @@ void lead(ppg_ctx *ctx, ChunkService &svc, std::unique_lock<std::mutex> &lk, int
     // async requests go to the copier, which marks them done once their results are in the caller's
     // buffers (the copies of a 256-chunk launch take about as long as the launch: done here, they
     // kept the launcher from leading the next one)
-    Svc::CopyTask task{i, {}};
+    ChunkService::CopyTask task{i, {}};
     for (ChunkReq *r : batch) {
         if (rc != PPG_OK) r->rc = rc;
         if (r->rc == PPG_OK && r->async) {

@@ -30,18 +30,13 @@
 // invalid after the next MoveNext, BatchedFASTQ.cs:56 / SURVEY Q9).  Order is canonical (chunk 0's
 // records, then chunk 1's, ...), not the reference's interleaving.
 #include "ppg_host.h"
+#include "ppg_launch.h"
 #include <fcntl.h>
 #include <unistd.h>
 #include <chrono>
 #include <condition_variable>
 #include <mutex>
 #include <thread>
-
-// launcher (ppg_parse.hip)
-hipError_t ppg_launch_pack_raw(hipStream_t s, const uint8_t *out, const PpgInflateJob *jobs, const PpgInflateResult *ires,
-                               const uint8_t *offs, const PpgOffsetRef *oref, const int64_t *raw_off, uint8_t *dst,
-                               int n, int blocks);
-hipError_t ppg_launch_copy16(hipStream_t s, const void *src, void *dst, uint64_t n16, int blocks);
 
 namespace {
 

@@ -1,5 +1,6 @@
 // ppg_host.h — host-side types shared by the translation units of libppgpu.so
-// (ppg_api.cpp: C ABI, index I/O, shards, ingest; ppg_index_gpu.cpp: GPU CreateIndex).
+// (ppg_api.cpp: C ABI, index I/O, shards, ingest; ppg_index_gpu.cpp: GPU CreateIndex; ppg_cursor.cpp: record
+// streaming; ppg_chunk.cpp + ppg_find.cpp: per-chunk Decompress; ppg_comm.cpp + ppg_pairs.hip: multi-GPU).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <rccl/rccl.h>
@@ -144,8 +145,16 @@ struct PinnedBuf {
     }
 };
 
-// DecompressAll state over chunks [first, first+n) of an index (ppg_api.cpp); the cursor and the
-// multi-GPU entry points (ppg_multi.cpp) drive it through the functions below.
+// grow a buffer to `need` elements, by at least half again its size (no reallocation per call)
+template <class B>
+hipError_t grow_buf(B &b, size_t need) {
+    if (b.p && b.n >= need) return hipSuccess;
+    return b.alloc(std::max(need, b.n + b.n / 2));
+}
+
+// DecompressAll state over chunks [first, first+n) of an index (ppg_api.cpp); the cursor
+// (ppg_cursor.cpp), the per-chunk Decompress (ppg_chunk.cpp) and the pair check (ppg_pairs.hip)
+// drive it through the functions below.
 struct ppg_shard {
     ppg_ctx *ctx = nullptr;
     int32_t first = 0, n = 0;

@@ -14,6 +14,7 @@
 #include <stdint.h>
 #include <algorithm>
 #include "ppg_device.h"
+#include "ppg_launch.h"
 #include "ppg_huffman.h"
 
 namespace {
@@ -404,7 +405,7 @@ __global__ __launch_bounds__(1024) void ppg_resolve_fill_kernel(const uint8_t *_
     }
 }
 
-// Many short chains at once (the per-chunk Decompress path, ppg_chunk.cpp find_mat: one chain per
+// Many short chains at once (the per-chunk Decompress path, ppg_find.cpp find_mat: one chain per
 // chunk of ~16 pieces, up to 256 chunks a launch): one workgroup per chain, its steps serial with the
 // current history in LDS -- composing maps only pays for one long chain.  chains[c] = {wb, m, src}:
 //   W[wb] = windows[src],  W[wb + j + 1] = T_{slots[wb + j]}(W[wb + j]),  j < m - 1.

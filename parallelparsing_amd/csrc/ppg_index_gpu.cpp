@@ -33,6 +33,7 @@
 // a mismatch is PPG_DATA_ERROR.  The CRC is computed on the GPU over each pass-2 batch
 // (ppg_crc_kernel) and folded on the host (crc_fold below).
 #include "ppg_host.h"
+#include "ppg_launch.h"
 #include <zlib.h>
 #include <chrono>
 #include <cstdlib>
@@ -42,25 +43,6 @@
 #include <fcntl.h>
 #include <sys/mman.h>
 #include <unistd.h>
-
-hipError_t ppg_launch_inflate(hipStream_t s, int ring_bits, int lit_bits, const uint32_t *comp, uint64_t nwords,
-                              const PpgInflateJob *jobs, const uint8_t *dicts, uint8_t *out, PpgInflateResult *res,
-                              int njobs, uint32_t *nls);
-hipError_t ppg_launch_inflate_ix(hipStream_t s, const uint32_t *comp, uint64_t nwords, const PpgInflateJob *jobs,
-                                 const uint8_t *dicts, uint8_t *out, PpgInflateResult *res, PpgBlockEnd *blk,
-                                 int njobs);
-hipError_t ppg_launch_block_find(hipStream_t s, const uint32_t *comp, uint64_t nwords, const uint64_t *lo,
-                                 const uint64_t *hi, uint64_t *cand, int n, int sub);
-hipError_t ppg_launch_gather(hipStream_t s, const uint8_t *out, const uint8_t *dicts, const PpgGather *g, uint8_t *dst,
-                             const uint8_t *ref, uint32_t *diff, int n);
-hipError_t ppg_launch_at_stats(hipStream_t s, const uint8_t *out, const PpgSpan *spans, PpgAtStats *st, int n);
-hipError_t ppg_launch_resolve(hipStream_t s, const uint8_t *ta, const uint8_t *tb, const uint32_t *slots, int np,
-                              uint8_t *W, uint16_t *M);
-int ppg_resolve_groups(int np);
-hipError_t ppg_launch_crc(hipStream_t s, const uint8_t *out, uint64_t n, uint64_t pad, const uint32_t *tabs,
-                          uint32_t *seg_raw, uint64_t nseg);
-hipError_t ppg_launch_pack_blocks(hipStream_t s, const PpgBlockEnd *blk, const PpgInflateJob *jobs,
-                                  const PpgInflateResult *res, const uint64_t *pre, PpgBlockEnd *dense, int n);
 
 namespace {
 

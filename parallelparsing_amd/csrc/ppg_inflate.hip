@@ -29,6 +29,7 @@
 #include <stdio.h>
 #include <type_traits>
 #include "ppg_device.h"
+#include "ppg_launch.h"
 #include "ppg_huffman.h"
 #include <atomic>
 #include <mutex>

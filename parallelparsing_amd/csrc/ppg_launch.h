@@ -1,0 +1,79 @@
+// ppg_launch.h — the host launchers of every kernel, declared once, grouped by the defining .hip file:
+// that file and every translation unit that calls one include this, so a signature has one place to change.
+#pragma once
+#include <hip/hip_runtime.h>
+#include "ppg_device.h"
+
+// ---- ppg_inflate.hip ----
+size_t ppg_inflate_lds_bytes(int ring_bits, int lit_bits);
+hipError_t ppg_launch_inflate(hipStream_t s, int ring_bits, int lit_bits, const uint32_t *comp, uint64_t nwords,
+                              const PpgInflateJob *jobs, const uint8_t *dicts, uint8_t *out, PpgInflateResult *res,
+                              int njobs, uint32_t *nls);
+hipError_t ppg_launch_inflate_ix(hipStream_t s, const uint32_t *comp, uint64_t nwords, const PpgInflateJob *jobs,
+                                 const uint8_t *dicts, uint8_t *out, PpgInflateResult *res, PpgBlockEnd *blk,
+                                 int njobs);
+hipError_t ppg_launch_inflate_ixf(hipStream_t s, const uint32_t *comp, uint64_t nwords, const PpgInflateJob *jobs,
+                                  const uint8_t *dicts, uint8_t *out, PpgInflateResult *res, PpgBlockEnd *blk,
+                                  int njobs);
+hipError_t ppg_launch_materialize(hipStream_t s, const uint16_t *sym, const uint8_t *wins, const PpgMatInfo *mi,
+                                  const PpgInflateJob *jobs, uint8_t *out, PpgInflateResult *res, int njobs,
+                                  uint32_t *nls);
+
+// ---- ppg_parse.hip ----
+hipError_t ppg_launch_parse_count(hipStream_t s, const uint8_t *out, const PpgInflateJob *jobs,
+                                  const PpgInflateResult *ires, const uint8_t *offs, const PpgOffsetRef *oref,
+                                  PpgParseInfo *info, uint64_t *base, uint64_t *total, int n, const uint32_t *nls);
+hipError_t ppg_launch_total_to_host(hipStream_t s, const uint64_t *total, uint64_t *host);
+hipError_t ppg_launch_parse_emit(hipStream_t s, const uint8_t *out, const PpgInflateJob *jobs,
+                                 const PpgInflateResult *ires, const uint8_t *offs, const PpgOffsetRef *oref,
+                                 PpgParseInfo *info, const uint64_t *base, const uint32_t *nls, uint32_t *recs,
+                                 uint64_t cap, int n);
+hipError_t ppg_launch_record_keys(hipStream_t s, const uint8_t *out, const PpgInflateJob *jobs,
+                                  const PpgInflateResult *ires, const uint8_t *offs, const PpgOffsetRef *oref,
+                                  const PpgParseInfo *info, const uint64_t *base, const uint32_t *recs, int64_t *keys,
+                                  int n);
+hipError_t ppg_launch_pack_raw(hipStream_t s, const uint8_t *out, const PpgInflateJob *jobs, const PpgInflateResult *ires,
+                               const uint8_t *offs, const PpgOffsetRef *oref, const int64_t *raw_off, uint8_t *dst,
+                               int n, int blocks);
+hipError_t ppg_launch_copy16(hipStream_t s, const void *src, void *dst, uint64_t n16, int blocks);
+hipError_t ppg_launch_split_merge(hipStream_t s, const PpgInflateJob *sjobs, const PpgInflateResult *sres,
+                                  const uint32_t *inv, const uint32_t *sidx, const uint32_t *snls,
+                                  const PpgInflateJob *jobs, PpgInflateResult *res, uint32_t *nls, int n);
+
+// ---- ppg_index.hip ----
+hipError_t ppg_launch_block_find(hipStream_t s, const uint32_t *comp, uint64_t nwords, const uint64_t *lo,
+                                 const uint64_t *hi, uint64_t *cand, int n, int sub);
+hipError_t ppg_launch_gather(hipStream_t s, const uint8_t *out, const uint8_t *dicts, const PpgGather *g, uint8_t *dst,
+                             const uint8_t *ref, uint32_t *diff, int n);
+hipError_t ppg_launch_at_stats(hipStream_t s, const uint8_t *out, const PpgSpan *spans, PpgAtStats *st, int n);
+hipError_t ppg_launch_pack_blocks(hipStream_t s, const PpgBlockEnd *blk, const PpgInflateJob *jobs,
+                                  const PpgInflateResult *res, const uint64_t *pre, PpgBlockEnd *dense, int n);
+int ppg_resolve_groups(int np);
+hipError_t ppg_launch_resolve(hipStream_t s, const uint8_t *ta, const uint8_t *tb, const uint32_t *slots, int np,
+                              uint8_t *W, uint16_t *M);
+hipError_t ppg_launch_resolve_chains(hipStream_t s, const uint8_t *ta, const uint32_t *slots, const uint4 *chains,
+                                     int nchains, const uint8_t *windows, uint8_t *W);
+hipError_t ppg_launch_pick_windows(hipStream_t s, const uint8_t *src, const uint32_t *idx, int n, uint8_t *dst);
+hipError_t ppg_launch_crc(hipStream_t s, const uint8_t *out, uint64_t n, uint64_t pad, const uint32_t *tabs,
+                          uint32_t *seg_raw, uint64_t nseg);
+
+// ---- ppg_seqpack.hip ----
+// Weak: libppgpu.so always links that object, but the host-only sanitizer build (tests/native) links
+// the host translation units with the kernel objects of inflate / parse / index alone; there the
+// packed-read entry points fail with PPG_UNSUPPORTED (seq_linked, ppg_api.cpp) instead of the link
+// failing.  There is no other implementation to fall back to.  (ppg_seqpack.hip includes this header
+// as well, which makes its definitions weak symbols: they are the only ones, so they link the same.)
+#define PPG_WEAK __attribute__((weak))
+PPG_WEAK hipError_t ppg_launch_seq_totals(hipStream_t s, const PpgInflateResult *ires, const PpgParseInfo *info,
+                                          const uint64_t *base, const uint32_t *recs, uint64_t *ctot, int n);
+PPG_WEAK hipError_t ppg_launch_seq_scan(hipStream_t s, const uint64_t *ctot, uint64_t *cbase, uint64_t *host_total,
+                                        int n);
+PPG_WEAK hipError_t ppg_launch_seq_offsets(hipStream_t s, const PpgInflateResult *ires, const PpgParseInfo *info,
+                                           const uint64_t *base, const uint32_t *recs, const uint64_t *cbase,
+                                           int64_t carry, int64_t *seq_off, uint32_t *seq_len, int n);
+PPG_WEAK hipError_t ppg_launch_seq_pack(hipStream_t s, const uint8_t *out, const PpgInflateJob *jobs,
+                                        const PpgInflateResult *ires, const uint8_t *offs, const PpgOffsetRef *oref,
+                                        const PpgParseInfo *info, const uint64_t *base, const uint32_t *recs,
+                                        const uint64_t *cbase, const int64_t *seq_off, const uint32_t *seq_len,
+                                        int64_t carry, uint64_t total, uint32_t *bases, uint32_t *mask, uint8_t *qual,
+                                        int n);

@@ -21,6 +21,7 @@
 //   compare   ppg_pair_compare counts pairs whose keys differ or are missing (< 0) and finds the
 //             first one; the counts of the two files must agree too.
 #include "ppg_host.h"
+#include "ppg_launch.h"
 #include <chrono>
 
 namespace {
@@ -150,11 +151,6 @@ extern "C" __global__ __launch_bounds__(256) void ppg_pack_segs(const PpgPackSeg
             ddesc[4 * s.ddst + i] = (uint32_t)((int64_t)s.desc[i] + s.delta);
     }
 }
-
-hipError_t ppg_launch_record_keys(hipStream_t s, const uint8_t *out, const PpgInflateJob *jobs,
-                                  const PpgInflateResult *ires, const uint8_t *offs, const PpgOffsetRef *oref,
-                                  const PpgParseInfo *info, const uint64_t *base, const uint32_t *recs, int64_t *keys,
-                                  int n);
 
 // a shard's state around a batch run again for emission (rerun_launch / rerun_collect)
 struct RerunSave {

@@ -16,6 +16,7 @@
 #include <stdlib.h>
 #include <algorithm>
 #include "ppg_device.h"
+#include "ppg_launch.h"
 
 // ------------------------------------------------------------------------------------------
 // FASTQ record scan.  raw_k = offset_k ++ out[out_off, out_off+produced).

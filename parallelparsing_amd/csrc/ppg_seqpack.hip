@@ -32,6 +32,7 @@
 #include <stdint.h>
 #include <algorithm>
 #include "ppg_device.h"
+#include "ppg_launch.h"
 
 namespace {
 

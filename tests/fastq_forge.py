@@ -376,7 +376,7 @@ def split_chunks():
     return lay.chunks
 
 
-LONE_RANGE = 16 * 1024          # kMatMinRange of ppg_chunk.cpp
+LONE_RANGE = 16 * 1024          # kMatMinRange of ppg_find.cpp
 ALNUM = np.frombuffer(b"0123456789ABCDEFGHIJKLMNOPQRSTUVWXYZabcdefghijklmnopqrstuvwxyz", np.uint8)
 
 

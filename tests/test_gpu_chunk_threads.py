@@ -124,11 +124,14 @@ def test_threads_200k_records_vs_oracle(file200k):
     assert st["split_chunks"] > n and st["side_points"] >= st["split_chunks"], st
 
 
-def test_lone_chunks_found_side_points_vs_oracle():
+@pytest.mark.parametrize("mat", [True, False])
+def test_lone_chunks_found_side_points_vs_oracle(mat):
     """Chunks of 40,000 records (~4 MB of gzip) decoded one call at a time: each launch holds one
     chunk, whose inner block starts are found on the GPU (candidates, speculative symbolic decode,
     the verified chain from the chunk's Point, resolved histories) -- it is decoded as ~16 waves.
-    Bytes and records equal the oracle's, and equal the one-wave decode (PPG_CHUNK_NO_FIND)."""
+    Bytes and records equal the oracle's, and equal the one-wave decode (PPG_CHUNK_NO_FIND).
+    mat: the materialise path (the default for plain indexes), or with PPG_CHUNK_NO_MAT the
+    two-decode path (16 ranges of >= 48 KiB), which otherwise runs only in mixed launches."""
     import os
     gz = synth_gz(130_000, 11)
     oi = O.build_index(gz, 40_000)
@@ -139,7 +142,12 @@ def test_lone_chunks_found_side_points_vs_oracle():
     before = dev.decompress_chunk_stats()
     for k in range(n):
         b = O.extract(gz, oi, k)
-        got, buf, rec = pp.Core.ExtractDeflateIndex(slice_of(gz, ix, k), ix, k, device=dev, with_records=True)
+        if not mat:
+            os.environ["PPG_CHUNK_NO_MAT"] = "1"
+        try:
+            got, buf, rec = pp.Core.ExtractDeflateIndex(slice_of(gz, ix, k), ix, k, device=dev, with_records=True)
+        finally:
+            os.environ.pop("PPG_CHUNK_NO_MAT", None)
         assert got == len(b) and sha(buf[:got]) == sha(b), k
         assert np.array_equal(rec, O.parse(oi.point(k)[4], b)), k
         os.environ["PPG_CHUNK_NO_FIND"] = "1"
@@ -199,6 +207,25 @@ def test_threads_side_points_split_chunks(file200k):
         assert sha(b) == exp[k][0], k
         assert np.array_equal(rec, exp[k][1]), k
     chunk_calls(gz, ix, dev, list(range(n)), check)
+
+
+def test_mixed_plain_and_side_point_indexes(file200k):
+    """Two indexes of one member, one plain (no side points) and one with side points, their chunks
+    0..15 queued interleaved on one device: a launch that holds both kinds takes the two-decode path
+    (the index's side points for one, the GPU block search for the other).  Every result equals the
+    oracle's, whichever launches the requests shared."""
+    gz, exp = file200k
+    dev = pp.Device(0)
+    plain = pp.Core.BuildDeflateIndex(gz, 2000)
+    side = pp.Core.BuildDeflateIndexGpu(gz, 2000, device=dev, side_bytes=64 << 10)
+    assert len(plain.side_points()[0]) == 0 and len(side.side_points()[0]) > side.Count
+    assert plain.Count == side.Count == len(exp) + 1
+    futs = [(k, pp.Core.ExtractDeflateIndexAsync(slice_of(gz, ix, k), ix, k, device=dev))
+            for k in range(16) for ix in (plain, side)]
+    for k, f in futs:
+        got, buf, rec = f.result()
+        assert sha(buf[:got]) == exp[k][0], k
+        assert np.array_equal(rec, exp[k][1]), k
 
 
 def test_bad_requests_fail_alone(file200k):
