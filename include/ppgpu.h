@@ -289,6 +289,50 @@ int ppg_shard_set_seqpack(ppg_shard *sh, int64_t *dev_seq_off, uint32_t *dev_seq
                           uint32_t *dev_bases, uint32_t *dev_mask, uint8_t *dev_qual, int64_t base_cap);
 int ppg_shard_seqpack_ready(ppg_shard *sh, int64_t *total_bases);
 
+/* ---- sequence queries: pattern search and base census over every FastqRecord.Sequence ----
+ * The reference's consumers beside Count(): RunPattern (Benchmark/Naive.cs: the records whose
+ * Sequence.Contains(pattern)) and the base count of Decompressor/Program.cs:20-21
+ * (Sequence.Count(c => c == 'A')), computed on the GPU from the resident output and descriptors; the
+ * answers are a few integers and one bit per record, no text leaves the device.
+ * For shard record j (numbered as above) with descriptor (n1,n2,n3,n4) relative to raw_k, S_j is the
+ * Sequence slice raw_k[n1+1, n2) of length L_j = n2 - n1 - 1 (a CRLF file's '\r' is part of it;
+ * records the reference parses twice, SURVEY Q1, count twice; a chunk whose status is not 0
+ * contributes no hits and no bases).
+ *   hit_j   1 iff the pattern occurs in S_j as a contiguous byte string (ordinal, case sensitive, as
+ *           string.Contains on the ASCII decode), wholly inside S_j.  pattern_len m: 0 <= m <= 64,
+ *           any byte but '\n'; m = 0 (or a NULL pattern) is a census alone and every record is a hit
+ *           (Contains("") is true).  m > 64, m < 0 or a '\n' in the pattern: PPG_ARG_ERROR.
+ *   census  count[0..3] bytes 'A' 'C' 'G' 'T' (upper case only) over all S_j, count[4] every other
+ *           byte; bases = the sum of L_j = the sum of count.
+ * dev_hit_mask (optional): caller device memory on this GPU, 4-byte aligned, written on the ctx stream;
+ * bit j & 31 of word j >> 5 is hit_j.  rec_cap counts records and is a multiple of 32; every word
+ * below ceil(records / 32) is written whole (bits at and past `records` are 0), no word at or past
+ * rec_cap / 32 is written; records > rec_cap: PPG_BUF_ERROR, nothing written.  NULL with cap 0: no mask.
+ * chunk_hits (optional): host int64[n], the hits per chunk of the shard.  `result` (optional) points
+ * at a ppg_seq_query_result; it is spelled void * so that a binding passes its own struct's address.
+ *  ppg_shard_query_seq       a one-batch shard after its run, blocking like ppg_shard_pack_seq
+ *                            (PPG_ARG_ERROR for a NULL shard, one that has not run, a multi-batch
+ *                            shard, a bad pattern, mask or cap).
+ *  ppg_shard_set_seqquery    any number of batches: from the next run on every batch is scanned while
+ *                            its output is resident, record numbers and totals carried across batches.
+ *                            The pattern is copied at the call.  pattern NULL, pattern_len < 0, a NULL
+ *                            mask and cap 0 together turn it off.  A run with more records than
+ *                            rec_cap fails with PPG_BUF_ERROR.
+ *  ppg_shard_seqquery_ready  1, and the outputs filled, when the last run completed the query; else 0:
+ *                            none attached, attached after that run, or the run failed
+ *                            (PPG_ARG_ERROR, a negative value, for a NULL shard). */
+typedef struct {
+    int64_t records;   /* records scanned */
+    int64_t hits;      /* records whose Sequence contains the pattern */
+    int64_t bases;     /* sum of L_j */
+    int64_t count[5];  /* A, C, G, T, other */
+} ppg_seq_query_result;
+int ppg_shard_query_seq(ppg_shard *sh, const uint8_t *pattern, int32_t pattern_len, uint32_t *dev_hit_mask,
+                        int64_t rec_cap, int64_t *chunk_hits, void *result);
+int ppg_shard_set_seqquery(ppg_shard *sh, const uint8_t *pattern, int32_t pattern_len, uint32_t *dev_hit_mask,
+                           int64_t rec_cap);
+int ppg_shard_seqquery_ready(ppg_shard *sh, int64_t *chunk_hits, void *result);
+
 /* Device-resident per-chunk record counts (int64[n]) copied to caller device memory on this
  * GPU (the input of the cross-GPU all-gather). */
 int ppg_shard_counts_to_device(ppg_shard *sh, int64_t *dev_dst);

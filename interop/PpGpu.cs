@@ -55,6 +55,15 @@ public unsafe struct PpgPairResult     // ppg_pair_result
     public fixed long FirstKeys[2];
 }
 
+[StructLayout(LayoutKind.Sequential)]
+public unsafe struct PpgSeqQueryResult // ppg_seq_query_result
+{
+    public long Records;                // records scanned
+    public long Hits;                   // records whose Sequence contains the pattern
+    public long Bases;                  // sum of the Sequence lengths
+    public fixed long Count[5];         // A, C, G, T, other
+}
+
 internal static unsafe class PpGpu
 {
     const string Lib = "ppgpu";   // libppgpu.so from parallelparsing_amd/
@@ -134,6 +143,12 @@ internal static unsafe class PpGpu
     [DllImport(Lib)] public static extern int ppg_shard_set_seqpack(nint shard, long* devSeqOff, uint* devSeqLen,
         long recCap, uint* devBases, uint* devMask, byte* devQual, long baseCap);
     [DllImport(Lib)] public static extern int ppg_shard_seqpack_ready(nint shard, out long totalBases);
+    // sequence queries: Sequence.Contains(pattern) per record and the base census (result: a PpgSeqQueryResult*)
+    [DllImport(Lib)] public static extern int ppg_shard_query_seq(nint shard, byte* pattern, int patternLen,
+        uint* devHitMask, long recCap, long* chunkHits, void* result);
+    [DllImport(Lib)] public static extern int ppg_shard_set_seqquery(nint shard, byte* pattern, int patternLen,
+        uint* devHitMask, long recCap);
+    [DllImport(Lib)] public static extern int ppg_shard_seqquery_ready(nint shard, long* chunkHits, void* result);
     [DllImport(Lib)] public static extern int ppg_shard_counts_to_device(nint shard, long* devDst);
     [DllImport(Lib)] public static extern int ppg_shard_timing(nint shard, out float inflateMs, out float parseMs,
         out float totalMs);

@@ -556,6 +556,42 @@ class PackedReads:
         return np.asarray(self.qual[b:b + L], np.uint8).tobytes()
 
 
+def _pattern_arg(pattern):
+    """(pointer argument, length) of a query pattern: bytes, str (ASCII) or None / empty for none."""
+    if pattern is None:
+        return None, 0
+    b = pattern.encode("ascii") if isinstance(pattern, str) else bytes(pattern)
+    return (C.c_uint8 * max(len(b), 1)).from_buffer_copy(b or b"\0"), len(b)
+
+
+class SeqQuery:
+    """The result of a sequence query (include/ppgpu.h "sequence queries"): `records` scanned, `hits`
+    (records whose Sequence contains the pattern; all of them without a pattern), `bases` (the sum of
+    the Sequence lengths), `counts` (bytes 'A' 'C' 'G' 'T' and every other byte over all Sequences),
+    `chunk_hits` (numpy int64, hits per chunk of the shard) and `hit_mask`: a uint32 CUDA tensor with
+    bit j & 31 of word j >> 5 set iff shard record j is a hit, or None when no mask was asked for."""
+
+    CLASSES = ("A", "C", "G", "T", "other")
+
+    def __init__(self, result, chunk_hits, hit_mask=None):
+        self.records, self.hits, self.bases = int(result.records), int(result.hits), int(result.bases)
+        self.counts = {c: int(v) for c, v in zip(self.CLASSES, result.count)}
+        self.chunk_hits = chunk_hits
+        self.hit_mask = hit_mask
+
+    def hit_records(self):
+        """The shard record numbers of the hits, ascending: an int64 tensor on the mask's device."""
+        if self.hit_mask is None:
+            raise ValueError("SeqQuery.hit_records: the query was made without a mask")
+        import torch
+        w = self.hit_mask.view(torch.int32)[:(self.records + 31) // 32]
+        bit = torch.arange(32, dtype=torch.int32, device=w.device)
+        return ((w[:, None] >> bit) & 1).reshape(-1).nonzero().reshape(-1)
+
+    def __repr__(self):
+        return f"SeqQuery(records={self.records}, hits={self.hits}, bases={self.bases}, counts={self.counts})"
+
+
 class Shard:
     """DecompressAll over index chunks [first, first+n) resident on one GPU (ppg_shard)."""
 
@@ -598,8 +634,9 @@ class Shard:
             self.dev.after_torch()
 
     def run(self):
-        if self._on_device or getattr(self, "_seqpack", None) is not None:
-            self._torch_order()   # the caller may have rewritten comp (or the set_seqpack planes) since the last run
+        hooked = getattr(self, "_seqpack", None) is not None or getattr(self, "_sq_mask", None) is not None
+        if self._on_device or hooked:
+            self._torch_order()   # the caller may have rewritten comp (or the hooks' tensors) since the last run
         check(lib.ppg_shard_run(self._h), "DecompressAll")
         return self
 
@@ -700,6 +737,55 @@ class Shard:
         if ok and p is not None:
             p.records, p.total_bases = self.total_records, tot.value
         return ok
+
+    def query_sequences(self, pattern=None, mask=False):
+        """Pattern search and base census over the Sequences of a one-batch shard after its run
+        (ppg_shard_query_seq), as a SeqQuery.  pattern: up to 64 bytes without '\\n' (None or empty:
+        the census alone, every record a hit); mask=True also returns the per-record hit bits as a
+        uint32 CUDA tensor on this device.  Ordered after torch's stream, complete on return."""
+        pat, m = _pattern_arg(pattern)
+        hm, cap = None, 0
+        if mask:
+            import torch
+            cap = (max(self.total_records, 0) + 31) // 32 * 32
+            dev = torch.device("cuda", self.dev.device)
+            hm = torch.zeros(cap // 32, dtype=torch.int32, device=dev).view(torch.uint32)
+        self._torch_order()
+        res, ch = _lib.PpgSeqQueryResult(), np.zeros(self.n, np.int64)
+        check(lib.ppg_shard_query_seq(self._h, pat, m, C.c_void_p(hm.data_ptr()) if cap else None, cap, _ptr(ch),
+                                      C.byref(res)), "query_sequences")
+        return SeqQuery(res, ch, hm)
+
+    def set_seqquery(self, pattern, mask=None):
+        """From the next run on, every output batch is searched for `pattern` and its bases counted
+        while its output is resident (ppg_shard_set_seqquery): works for shards of any number of
+        batches; the result is `seqquery` after the run.  pattern as in query_sequences, b"" for
+        the census alone; None turns the hook off.  mask: an int32 / uint32 CUDA tensor on this
+        device of at least ceil(records / 32) words that receives the hit bits, or None."""
+        if pattern is None:
+            check(lib.ppg_shard_set_seqquery(self._h, None, -1, None, 0), "set_seqquery")
+            self._sq_mask = None
+            return self
+        pat, m = _pattern_arg(pattern)
+        ptr, cap = None, 0
+        if mask is not None:
+            import torch
+            if not (mask.is_cuda and mask.dtype in (torch.int32, torch.uint32) and mask.is_contiguous()):
+                raise ValueError("set_seqquery: mask must be a contiguous int32 / uint32 CUDA tensor")
+            ptr, cap = C.c_void_p(mask.data_ptr()), 32 * mask.numel()
+            mask = mask.view(torch.uint32)
+        self._sq_mask = mask   # kept alive while the library may write it
+        self._torch_order()
+        check(lib.ppg_shard_set_seqquery(self._h, pat, m, ptr if cap else None, cap), "set_seqquery")
+        return self
+
+    @property
+    def seqquery(self):
+        """The SeqQuery of the last run's set_seqquery hook, or None when that run did not complete one."""
+        res, ch = _lib.PpgSeqQueryResult(), np.zeros(self.n, np.int64)
+        if lib.ppg_shard_seqquery_ready(self._h, _ptr(ch), C.byref(res)) != 1:
+            return None
+        return SeqQuery(res, ch, getattr(self, "_sq_mask", None))
 
     def results(self):
         n = self.n
@@ -988,6 +1074,7 @@ class BatchedFASTQ:
         self.enable_ssd_optimization = enable_ssd_optimization
         self.dev = device
         self._shard = None
+        self._qshard = None   # CountPattern / CountBases: (out_capacity, Shard), kept until Dispose()
         # one rank of a multi-GPU job (the reference's Task.Run fan-out, BatchedFASTQ.cs:62-77, on
         # GPUs): iteration yields this rank's share -- the contiguous chunk range ppg_partition
         # gives it -- so the ranks' records, concatenated in rank order, are the file's
@@ -1052,5 +1139,37 @@ class BatchedFASTQ:
         finally:
             cur.close()
 
+    # decompressed bytes resident per batch of CountPattern / CountBases: the shard runs the file in
+    # batches of whole chunks no larger than this, so a file of any size is scanned in bounded memory
+    query_out_capacity = 256 << 20
+
+    def _query(self, pattern):
+        if self.world is not None:
+            raise ValueError("CountPattern / CountBases run in a single process (no rank / world)")
+        cap, sh = getattr(self, "_qshard", None) or (None, None)
+        if sh is None or cap != self.query_out_capacity:
+            # the file's compressed bytes go to the device once (from the page cache, no host copy) and
+            # stay there with one batch of output until Dispose(): a second query only runs again
+            n = self.index.Count - 1
+            _, i0, _, _ = self.index.point_fields(0)
+            _, i1, _, _ = self.index.point_fields(n)
+            comp = np.memmap(self.gzip_path, np.uint8, "r", offset=i0 - 1, shape=(i1 - i0 + 1,))
+            cap = self.query_out_capacity
+            sh = Shard(self.index, comp, 0, n, device=self.dev, out_capacity=cap)
+            self._qshard = (cap, sh)
+        return sh.set_seqquery(pattern).run().seqquery
+
+    def CountPattern(self, pattern):
+        """Number of records whose Sequence contains `pattern` (Benchmark/Naive.cs RunPattern:
+        records.Count(r => r.Sequence.Contains(pattern))), searched on the GPU batch by batch
+        (Shard.set_seqquery): no record text reaches the host."""
+        return self._query(b"" if pattern is None else pattern).hits
+
+    def CountBases(self):
+        """{'A', 'C', 'G', 'T', 'other'}: the bytes of every Sequence by class (Decompressor/Program.cs:20-21
+        counts the 'A's this way), counted on the GPU batch by batch."""
+        return dict(self._query(b"").counts)
+
     def Dispose(self):
         self._shard = None
+        self._qshard = None

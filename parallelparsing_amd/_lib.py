@@ -121,6 +121,9 @@ _SIGS = {
     "ppg_shard_pack_seq": (C.c_int, [vp, vp, vp, i64, vp, vp, vp, i64, P(i64)]),
     "ppg_shard_set_seqpack": (C.c_int, [vp, vp, vp, i64, vp, vp, vp, i64]),
     "ppg_shard_seqpack_ready": (C.c_int, [vp, P(i64)]),
+    "ppg_shard_query_seq": (C.c_int, [vp, vp, i32, vp, i64, vp, vp]),
+    "ppg_shard_set_seqquery": (C.c_int, [vp, vp, i32, vp, i64]),
+    "ppg_shard_seqquery_ready": (C.c_int, [vp, vp, vp]),
     "ppg_cursor_open_packed": (C.c_int, [vp, vp, C.c_char_p, i32, i32, i64, C.c_int, i32, P(vp)]),
     "ppg_cursor_packed": (C.c_int, [vp, P(vp), P(vp), P(vp), P(vp), P(i64)]),
     "ppg_cursor_packed_offsets": (C.c_int, [vp, vp, i64]),
@@ -160,6 +163,11 @@ class PpgPairResult(C.Structure):
     """ppg_pair_result (include/ppgpu.h)."""
     _fields_ = [("pairs", C.c_int64), ("records", C.c_int64 * 2), ("duplicates", C.c_int64 * 2),
                 ("mismatches", C.c_int64), ("first_bad", C.c_int64), ("first_keys", C.c_int64 * 2)]
+
+
+class PpgSeqQueryResult(C.Structure):
+    """ppg_seq_query_result (include/ppgpu.h)."""
+    _fields_ = [("records", C.c_int64), ("hits", C.c_int64), ("bases", C.c_int64), ("count", C.c_int64 * 5)]
 
 
 for _name, (_res, _args) in _SIGS.items():

@@ -36,6 +36,10 @@ static bool seq_linked() {   // (weak references, ppg_launch.h: absent from the 
     return ppg_launch_seq_totals && ppg_launch_seq_scan && ppg_launch_seq_offsets && ppg_launch_seq_pack;
 }
 
+static bool seqquery_linked() {
+    return seq_linked() && ppg_launch_seq_query && ppg_launch_seq_query_chunks && ppg_launch_seq_query_totals;
+}
+
 namespace {
 
 // Byte source read in FileStream.Read(input, 0, CHUNK) steps (Core.cs:41).
@@ -681,6 +685,72 @@ static int seq_hook(ppg_shard *sh, int32_t b0, int32_t b1, int64_t tot) {
     return PPG_OK;
 }
 
+// ---- sequence queries (ppg_seqquery.hip) ----
+int shard_seq_query(ppg_shard *sh, int32_t b0, int32_t b1, const uint32_t *recs, int64_t rec0, int64_t tot,
+                    const PpgSeqPattern &pat, int32_t m, uint32_t *mask, bool first) {
+    hipStream_t s = shard_stream(sh);
+    const int nb = b1 - b0;
+    if (!seqquery_linked()) return PPG_UNSUPPORTED;
+    int64_t total = 0;
+    if (int rc = shard_seq_layout(sh, b0, b1, recs, &total)) return rc;
+    HIPCHK(grow_buf(sh->sq_off, (size_t)tot + 1));
+    HIPCHK(grow_buf(sh->sq_len, (size_t)tot + 1));
+    HIPCHK(sh->sq_acc.alloc(8));
+    HIPCHK(sh->sq_host.alloc(8 * (8 + (size_t)sh->n)));
+    if (first) HIPCHK(hipMemsetAsync(sh->sq_acc.p, 0, 64, s));
+    // the hit bits: the caller's mask at the shard record number, else (a pattern, no mask) scratch
+    // at the batch's record number; a census alone with no mask needs none
+    uint32_t *words = mask;
+    uint64_t bit0 = (uint64_t)rec0;
+    if (!mask && m > 0) {
+        HIPCHK(grow_buf(sh->sq_bits, (size_t)tot / 32 + 1));
+        words = sh->sq_bits.p;
+        bit0 = 0;
+    }
+    if (words) {
+        // the words whose first bit is this batch's or later; the word a batch shares with the one
+        // before it was cleared by that batch
+        const uint64_t w0 = (bit0 + 31) / 32, w1 = (bit0 + (uint64_t)tot + 31) / 32;
+        if (w1 > w0) HIPCHK(hipMemsetAsync(words + w0, 0, 4 * (size_t)(w1 - w0), s));
+    }
+    HIPCHK(ppg_launch_seq_offsets(s, sh->res.p + b0, sh->info.p + b0, sh->base.p + b0, recs, sh->sp_cbase.p, 0,
+                                  sh->sq_off.p, sh->sq_len.p, nb));
+    HIPCHK(ppg_launch_seq_query(s, sh->out.p, sh->jobs.p + b0, sh->offs.p, sh->oref.p + b0, sh->info.p + b0,
+                                sh->base.p + b0, recs, sh->sp_cbase.p, sh->sq_off.p, sh->sq_len.p, (uint64_t)total, &pat,
+                                m, words, bit0, sh->sq_acc.p, nb));
+    int64_t *host = (int64_t *)sh->sq_host.p;
+    HIPCHK(ppg_launch_seq_query_chunks(s, sh->res.p + b0, sh->info.p + b0, sh->base.p + b0, m, words, bit0,
+                                       sh->sq_acc.p, host + 8 + b0, nb));
+    HIPCHK(ppg_launch_seq_query_totals(s, sh->sq_acc.p, host));
+    return PPG_OK;
+}
+
+// what the last completed query left in pinned memory
+static void seqquery_outputs(const ppg_shard *sh, int64_t *chunk_hits, void *result) {
+    const int64_t *host = (const int64_t *)sh->sq_host.p;
+    if (!host) {   // a shard without chunks: no batch ran
+        if (result) memset(result, 0, sizeof(ppg_seq_query_result));
+        return;
+    }
+    if (result) memcpy(result, host, sizeof(ppg_seq_query_result));
+    if (chunk_hits && sh->n) memcpy(chunk_hits, host + 8, 8 * (size_t)sh->n);
+}
+
+// m bytes of pattern (NULL: m = 0) as the kernel's argument; false for a length outside [0, 64] or a '\n'
+static bool seqquery_pattern(const uint8_t *pattern, int32_t m, PpgSeqPattern *pat) {
+    if (m < 0 || m > 64 || (m > 0 && !pattern)) return false;
+    memset(pat, 0, sizeof *pat);
+    for (int32_t i = 0; i < m; i++) {
+        if (pattern[i] == '\n') return false;
+        pat->w[i >> 3] |= (uint64_t)pattern[i] << (8 * (i & 7));
+    }
+    return true;
+}
+
+static bool seqquery_mask_ok(const uint32_t *mask, int64_t rec_cap) {
+    return rec_cap >= 0 && rec_cap % 32 == 0 && ((uintptr_t)mask & 3) == 0 && (mask != nullptr || rec_cap == 0);
+}
+
 // Enqueue one batch [b0, b1) on the shard's stream, with no host synchronisation: inflate (+ the
 // fused newline census), per-chunk counts and their scan, the record total into pinned host
 // memory, then the descriptors, whose writes stop at the descriptor buffer's size.
@@ -765,6 +835,13 @@ int batch_collect(ppg_shard *sh, int32_t b0, int32_t b1, float &total_ms) {
     // packed reads of the batch, likewise while its output is resident (ppg_shard_set_seqpack)
     if (sh->sp_off)
         if (int rc = seq_hook(sh, b0, b1, (int64_t)tot)) return rc;
+    // sequence query of the batch, likewise (ppg_shard_set_seqquery)
+    if (sh->sq_on) {
+        if (sh->sq_mask && sh->total_records + (int64_t)tot > sh->sq_rec_cap) return PPG_BUF_ERROR;
+        if (int rc = shard_seq_query(sh, b0, b1, sh->recs.p + r0, sh->total_records, (int64_t)tot, sh->sq_pat, sh->sq_m,
+                                     sh->sq_mask, b0 == 0))
+            return rc;
+    }
     sh->t_inflate += a;
     sh->t_parse += b + c;
     total_ms += a + b + c;
@@ -813,9 +890,11 @@ int ppg_shard_run(ppg_shard *sh) {
     if (!sh) return PPG_ARG_ERROR;
     sh->keys_written = 0;
     sh->sp_written = 0;
+    sh->sq_written = 0;
     sh->last_rc = shard_run(sh);
     sh->keys_written = sh->last_rc == PPG_OK && sh->keys_dev != nullptr;
     sh->sp_written = sh->last_rc == PPG_OK && sh->sp_off != nullptr;
+    sh->sq_written = sh->last_rc == PPG_OK && sh->sq_on;
     return sh->last_rc;
 }
 
@@ -1099,6 +1178,47 @@ int ppg_shard_seqpack_ready(ppg_shard *sh, int64_t *total_bases) {
     return 1;
 }
 
+// ---- sequence queries: the packed reads entry points' counterparts ----
+int ppg_shard_query_seq(ppg_shard *sh, const uint8_t *pattern, int32_t pattern_len, uint32_t *dev_hit_mask,
+                        int64_t rec_cap, int64_t *chunk_hits, void *result) {
+    PpgSeqPattern pat;
+    if (!sh || !sh->ran || sh->batches.size() != 1 || !seqquery_pattern(pattern, pattern_len, &pat) ||
+        !seqquery_mask_ok(dev_hit_mask, rec_cap))
+        return PPG_ARG_ERROR;
+    if (!seqquery_linked()) return PPG_UNSUPPORTED;
+    if (dev_hit_mask && sh->total_records > rec_cap) return PPG_BUF_ERROR;
+    HIPCHK(hipSetDevice(sh->ctx->device));
+    sh->sq_written = 0;   // the pinned outputs are rewritten: an earlier run's hook result is gone
+    if (int rc = shard_seq_query(sh, 0, sh->n, sh->recs.p, 0, sh->total_records, pat, pattern_len, dev_hit_mask, true))
+        return rc;
+    HIPCHK(hipStreamSynchronize(shard_stream(sh)));
+    seqquery_outputs(sh, chunk_hits, result);
+    return PPG_OK;
+}
+
+int ppg_shard_set_seqquery(ppg_shard *sh, const uint8_t *pattern, int32_t pattern_len, uint32_t *dev_hit_mask,
+                           int64_t rec_cap) {
+    if (!sh) return PPG_ARG_ERROR;
+    const bool off = !pattern && pattern_len < 0 && !dev_hit_mask && !rec_cap;
+    PpgSeqPattern pat = {};
+    if (!off && (!seqquery_pattern(pattern, pattern_len, &pat) || !seqquery_mask_ok(dev_hit_mask, rec_cap)))
+        return PPG_ARG_ERROR;
+    sh->sq_on = off ? 0 : 1;
+    sh->sq_pat = pat;
+    sh->sq_m = off ? 0 : pattern_len;
+    sh->sq_mask = dev_hit_mask;
+    sh->sq_rec_cap = rec_cap;
+    sh->sq_written = 0;   // completed by the next run, not by an earlier one
+    return PPG_OK;
+}
+
+int ppg_shard_seqquery_ready(ppg_shard *sh, int64_t *chunk_hits, void *result) {
+    if (!sh) return PPG_ARG_ERROR;
+    if (!sh->sq_written) return 0;
+    seqquery_outputs(sh, chunk_hits, result);
+    return 1;
+}
+
 // Measurement hook of tools/seqpack_probe.py (not part of the ABI: no declaration in ppgpu.h).  On a
 // one-batch shard after its run, device time by hipEvents on the shard's stream, the median of reps
 // launches after one warm-up each, into ms[0..3]: layout totals + scan, seq_off / seq_len, the pack
@@ -1162,6 +1282,66 @@ int ppgx_seqpack_times(ppg_shard *sh, int quality, int reps, float *ms, int64_t 
     (void)hipEventDestroy(e1);
     bytes[0] = total / 4 + total / 8 + (quality ? total : 0) + 12 * nrec + 8;
     bytes[1] = raw_off[(size_t)sh->n];
+    return rc;
+}
+
+// Measurement hook of tools/seqquery_probe.py (not part of the ABI: no declaration in ppgpu.h).  On a
+// one-batch shard after its run, device time by hipEvents on the shard's stream, the median of reps
+// launches after one warm-up each, into ms[0..3]: layout totals + scan, seq_off / seq_len, the query
+// kernel (with the clearing of its hit bits when there is a pattern), and the per-chunk reduction +
+// the totals' store.  The accumulators keep adding over the launches: only the times are meaningful.
+int ppgx_seqquery_times(ppg_shard *sh, const uint8_t *pattern, int32_t m, int reps, float *ms) {
+    PpgSeqPattern pat;
+    if (!sh || !sh->ran || sh->batches.size() != 1 || !ms || reps < 1 || !seqquery_pattern(pattern, m, &pat))
+        return PPG_ARG_ERROR;
+    HIPCHK(hipSetDevice(sh->ctx->device));
+    hipStream_t s = shard_stream(sh);
+    // one whole query first: it sizes the scratch buffers and leaves the layout in place
+    const int64_t tot = sh->total_records;
+    if (int rc = shard_seq_query(sh, 0, sh->n, sh->recs.p, 0, tot, pat, m, nullptr, true)) return rc;
+    HIPCHK(hipStreamSynchronize(s));
+    const uint64_t total = *(volatile uint64_t *)sh->sp_htot.p;
+    uint32_t *words = m > 0 ? sh->sq_bits.p : nullptr;
+    int64_t *host = (int64_t *)sh->sq_host.p;
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    HIPCHK(hipEventCreate(&e0));
+    HIPCHK(hipEventCreate(&e1));
+    int rc = PPG_OK;
+    for (int what = 0; what < 4 && rc == PPG_OK; what++) {
+        std::vector<float> t;
+        for (int r = 0; r <= reps && rc == PPG_OK; r++) {
+            hipError_t e = hipEventRecord(e0, s);
+            if (e == hipSuccess && what == 0) {
+                e = ppg_launch_seq_totals(s, sh->res.p, sh->info.p, sh->base.p, sh->recs.p, sh->sp_ctot.p, sh->n);
+                if (e == hipSuccess) e = ppg_launch_seq_scan(s, sh->sp_ctot.p, sh->sp_cbase.p, (uint64_t *)sh->sp_htot.p, sh->n);
+            } else if (e == hipSuccess && what == 1) {
+                e = ppg_launch_seq_offsets(s, sh->res.p, sh->info.p, sh->base.p, sh->recs.p, sh->sp_cbase.p, 0, sh->sq_off.p,
+                                           sh->sq_len.p, sh->n);
+            } else if (e == hipSuccess && what == 2) {
+                if (words) e = hipMemsetAsync(words, 0, 4 * (size_t)((tot + 31) / 32), s);
+                if (e == hipSuccess)
+                    e = ppg_launch_seq_query(s, sh->out.p, sh->jobs.p, sh->offs.p, sh->oref.p, sh->info.p, sh->base.p,
+                                             sh->recs.p, sh->sp_cbase.p, sh->sq_off.p, sh->sq_len.p, total, &pat, m, words, 0,
+                                             sh->sq_acc.p, sh->n);
+            } else if (e == hipSuccess) {
+                e = ppg_launch_seq_query_chunks(s, sh->res.p, sh->info.p, sh->base.p, m, words, 0, sh->sq_acc.p, host + 8, sh->n);
+                if (e == hipSuccess) e = ppg_launch_seq_query_totals(s, sh->sq_acc.p, host);
+            }
+            if (e == hipSuccess) e = hipEventRecord(e1, s);
+            if (e == hipSuccess) e = hipEventSynchronize(e1);
+            float v = 0;
+            if (e == hipSuccess) e = hipEventElapsedTime(&v, e0, e1);
+            if (e != hipSuccess) rc = PPG_DEVICE_ERROR;
+            if (r) t.push_back(v);   // (r = 0 warms up)
+        }
+        if (rc == PPG_OK) {
+            std::sort(t.begin(), t.end());
+            ms[what] = t[t.size() / 2];
+        }
+    }
+    (void)hipEventDestroy(e0);
+    (void)hipEventDestroy(e1);
+    sh->sq_written = 0;   // the pinned outputs no longer belong to a run
     return rc;
 }
 

@@ -95,6 +95,11 @@ struct PpgSpan {          // byte range [lo, hi) of an output buffer
     uint64_t lo, hi;
 };
 
+// ppg_seq_query's pattern, a kernel argument: byte i is bits [8 (i & 7), + 8) of w[i >> 3] (m <= 64 bytes)
+struct PpgSeqPattern {
+    uint64_t w[8];
+};
+
 #define PPG_FLAG_NO_EOB 1     // the symbol after the last output byte is not end-of-block
 #define PPG_FLAG_OVERRUN 2    // decoding consumed bits past the chunk's compressed slice
 #define PPG_FLAG_BLK_FULL 16  // CreateIndex pass 1: more block ends than blk_cap

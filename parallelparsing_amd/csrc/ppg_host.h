@@ -202,6 +202,18 @@ struct ppg_shard {
     int sp_written = 0;     // the last successful run filled the planes (set by shard_run)
     DevBuf<uint64_t> sp_ctot, sp_cbase;   // per-chunk padded bases and their scan (n + 1 entries)
     PinnedBuf sp_htot;                    // the scan's total, stored by the kernel
+    // ppg_shard_set_seqquery: every batch is also searched for sq_pat and its bases counted
+    // (ppg_seqquery.hip); hit bits at the shard record number in sq_mask, totals carried in sq_acc
+    int sq_on = 0;
+    PpgSeqPattern sq_pat = {};
+    int32_t sq_m = 0;
+    uint32_t *sq_mask = nullptr;
+    int64_t sq_rec_cap = 0;
+    int sq_written = 0;                  // the last successful run completed the query (set by shard_run)
+    DevBuf<int64_t> sq_off;              // scratch: seq_off / seq_len of one batch's records
+    DevBuf<uint32_t> sq_len, sq_bits;    // sq_bits: a batch's hit bits when the caller gives no mask
+    DevBuf<uint64_t> sq_acc;             // records, hits, (unused), count[5] of the run so far
+    PinnedBuf sq_host;                   // a ppg_seq_query_result, then hits per chunk: stored by the kernels
     // split chunks (ppg_shard_set_split): the inflate launch runs sub-jobs, ppg_split_merge folds
     // them back into per-chunk results and census regions
     int32_t nsub = 0;                            // side points in use (0: one wave per chunk)
@@ -253,6 +265,12 @@ int shard_seq_reserve(ppg_shard *sh, int64_t nchunks);
 int shard_seq_layout(ppg_shard *sh, int32_t b0, int32_t b1, const uint32_t *recs, int64_t *total);
 int shard_seq_pack(ppg_shard *sh, int32_t b0, int32_t b1, const uint32_t *recs, int64_t carry, int64_t total,
                    int64_t *seq_off, uint32_t *seq_len, uint32_t *bases, uint32_t *mask, uint8_t *qual);
+// sequence query of chunks [b0, b1) of one resident batch (recs: the batch's first descriptor, rec0 its
+// first record's shard record number, tot its records), queued on the shard's stream after a layout
+// of its own (which blocks); first: the run's accumulators start from 0.  The totals so far and the
+// chunks' hits are in sq_host once the stream has drained.
+int shard_seq_query(ppg_shard *sh, int32_t b0, int32_t b1, const uint32_t *recs, int64_t rec0, int64_t tot,
+                    const PpgSeqPattern &pat, int32_t m, uint32_t *mask, bool first);
 
 // collectives of a ppg_comm beyond the count gather (ppg_comm.cpp), used by ppg_pairs.hip
 int comm_size(const ppg_comm *c, int32_t *rank, int32_t *nranks);

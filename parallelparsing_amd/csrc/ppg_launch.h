@@ -77,3 +77,16 @@ PPG_WEAK hipError_t ppg_launch_seq_pack(hipStream_t s, const uint8_t *out, const
                                         const uint64_t *cbase, const int64_t *seq_off, const uint32_t *seq_len,
                                         int64_t carry, uint64_t total, uint32_t *bases, uint32_t *mask, uint8_t *qual,
                                         int n);
+
+// ---- ppg_seqquery.hip ----
+// Weak for the same reason (seqquery_linked, ppg_api.cpp).
+PPG_WEAK hipError_t ppg_launch_seq_query(hipStream_t s, const uint8_t *out, const PpgInflateJob *jobs,
+                                         const uint8_t *offs, const PpgOffsetRef *oref, const PpgParseInfo *info,
+                                         const uint64_t *base, const uint32_t *recs, const uint64_t *cbase,
+                                         const int64_t *seq_off, const uint32_t *seq_len, uint64_t total,
+                                         const PpgSeqPattern *pat, int m, uint32_t *hit_words, uint64_t rec0,
+                                         uint64_t *acc, int n);
+PPG_WEAK hipError_t ppg_launch_seq_query_chunks(hipStream_t s, const PpgInflateResult *ires, const PpgParseInfo *info,
+                                                const uint64_t *base, int m, uint32_t *hit_words, uint64_t rec0,
+                                                uint64_t *acc, int64_t *host_chunk_hits, int n);
+PPG_WEAK hipError_t ppg_launch_seq_query_totals(hipStream_t s, const uint64_t *acc, int64_t *host_result);
