@@ -333,6 +333,56 @@ int ppg_shard_set_seqquery(ppg_shard *sh, const uint8_t *pattern, int32_t patter
                            int64_t rec_cap);
 int ppg_shard_seqquery_ready(ppg_shard *sh, int64_t *chunk_hits, void *result);
 
+/* ---- record selection: the records a mask selects, compacted on the GPU ----
+ * The body of RunPattern's loop (Benchmark/Naive.cs:168-179: foreach record, if Sequence.Contains)
+ * acts on the records that hit; a query above says which they are, this hands them over: the selected
+ * records' text, back to back, made on the GPU while the text is resident, so that only they cross
+ * the bus.  The mask is a query's hit mask or anything a consumer computed per record.
+ * Shard record j (numbered as above) is record q of chunk k with descriptor (n1,n2,n3,n4) relative to
+ * raw_k.  Its text is T_j = raw_k[a_j, e_j), a_j = 0 for q = 0 and (n4 of record q-1 of chunk k) + 1
+ * otherwise, e_j = n4 + 1, len_j = e_j - a_j: the bytes ppg_pairs_emit_* define per record, from its
+ * first byte through its quality line's '\n'.  A record the reference parses twice is
+ * record 0 of the next chunk; its T_j lies wholly inside the offset carry.
+ * Selected: bit j & 31 of dev_mask[j >> 5] (the hit-mask format), ANDed with "chunk k's status is 0"
+ * (a failed chunk contributes nothing, as in a query).  A NULL mask with mask_cap 0 selects every
+ * record.  Bits at and past `records` are ignored.  mask_cap counts records and is a multiple of 32,
+ * else PPG_ARG_ERROR; records > mask_cap: PPG_BUF_ERROR.
+ * Output, for the S selected records in ascending j (the i-th is j_i):
+ *   recno[i] = j_i (int64);
+ *   sel_off[0] = 0, sel_off[i+1] = sel_off[i] + len_{j_i} (int64: S + 1 entries, no 4 GiB limit);
+ *   bytes[sel_off[i], sel_off[i+1]) = T_{j_i}, back to back, no padding;
+ *   desc[4i .. 4i+3] = (n1 - a, n2 - a, n3 - a, n4 - a) (uint32), relative to the record's own first
+ *   byte: the field slices of ppg_shard_copy_records apply with r = 0.
+ * Nothing at or past sel_off[S] bytes or S records (S + 1 offsets) is written, and the output is a
+ * function of the text and the mask alone.  Buffers are caller device memory on this GPU, written on
+ * the ctx stream: dev_recno and dev_sel_off 8-byte aligned (sel_cap and sel_cap + 1 entries), dev_desc
+ * and dev_bytes 16-byte aligned (4 * sel_cap words, byte_cap bytes).  When S exceeds sel_cap or
+ * sel_off[S] exceeds byte_cap the call returns PPG_BUF_ERROR and nothing is written: the sizes are
+ * checked before anything is moved.
+ *  ppg_shard_select_size     after a run of any number of batches (the descriptors and statuses stay
+ *                            resident): S and sel_off[S], the caps a selection needs.  Blocking.
+ *  ppg_shard_select_records  a one-batch shard after its run, blocking like ppg_shard_query_seq;
+ *                            *records = S, *bytes = sel_off[S] (also with PPG_BUF_ERROR).
+ *                            PPG_ARG_ERROR for a NULL shard, one that has not run, a multi-batch
+ *                            shard, a bad cap, a misaligned or missing buffer.
+ *  ppg_shard_set_select      any number of batches: from the next run on every batch's selected records
+ *                            are appended while its output is resident, recno, sel_off and the bytes
+ *                            carried across batches.  It is the last of a batch's hooks: a
+ *                            ppg_shard_set_seqquery hook that writes the same mask buffer has filled
+ *                            this batch's bits before they are read.  A batch that would exceed a cap
+ *                            fails the run with PPG_BUF_ERROR.  All pointers NULL and caps 0 turn it off.
+ *  ppg_shard_select_ready    1, and S and sel_off[S] filled, when the last run completed the selection;
+ *                            else 0: none attached, attached after that run, or the run failed
+ *                            (PPG_ARG_ERROR, a negative value, for a NULL shard). */
+int ppg_shard_select_size(ppg_shard *sh, const uint32_t *dev_mask, int64_t mask_cap, int64_t *records, int64_t *bytes);
+int ppg_shard_select_records(ppg_shard *sh, const uint32_t *dev_mask, int64_t mask_cap, int64_t *dev_recno,
+                             int64_t *dev_sel_off, uint32_t *dev_desc, int64_t sel_cap, uint8_t *dev_bytes,
+                             int64_t byte_cap, int64_t *records, int64_t *bytes);
+int ppg_shard_set_select(ppg_shard *sh, const uint32_t *dev_mask, int64_t mask_cap, int64_t *dev_recno,
+                         int64_t *dev_sel_off, uint32_t *dev_desc, int64_t sel_cap, uint8_t *dev_bytes,
+                         int64_t byte_cap);
+int ppg_shard_select_ready(ppg_shard *sh, int64_t *records, int64_t *bytes);
+
 /* Device-resident per-chunk record counts (int64[n]) copied to caller device memory on this
  * GPU (the input of the cross-GPU all-gather). */
 int ppg_shard_counts_to_device(ppg_shard *sh, int64_t *dev_dst);
@@ -409,6 +459,26 @@ int ppg_cursor_open_packed(ppg_ctx *ctx, const ppg_index *ix, const char *gz_pat
 int ppg_cursor_packed(const ppg_cursor *c, uint32_t **bases, uint32_t **mask, uint8_t **qual, uint32_t **seq_len,
                       int64_t *total_bases);
 int ppg_cursor_packed_offsets(const ppg_cursor *c, int64_t *seq_off, int64_t cap);
+
+/* The filtered enumerator: as ppg_cursor_open, but every batch is queried for the pattern (the rules
+ * of ppg_shard_set_seqquery: 0 <= pattern_len <= 64, no '\n'; 0 or a NULL pattern selects every
+ * record), its hits are selected on the device ("record selection" above) and only the selection is
+ * copied to pinned host memory: host memory and PCIe traffic follow what is selected, not the batch.
+ * In a ppg_batch of such a cursor text and desc are NULL; nrecords counts the records scanned, and
+ * first_chunk, nchunks, record_base, raw_off and rec_off are filled as for a text cursor.
+ *  ppg_cursor_selected        the current batch's selected text and descriptors in pinned host memory
+ *                             (valid until the next ppg_cursor_next; any pointer may be NULL), the
+ *                             number of selected records and of their bytes;
+ *  ppg_cursor_selected_index  its records + 1 offsets (batch-relative, from 0) and its `records` record
+ *                             numbers copied to the caller (either may be NULL; cap counts records:
+ *                             PPG_BUF_ERROR when cap < records).  A record number counts among the
+ *                             records this cursor hands out: record_base + its number in the batch.
+ * Both return PPG_ARG_ERROR on other cursors and before the first ppg_cursor_next. */
+int ppg_cursor_open_select(ppg_ctx *ctx, const ppg_index *ix, const char *gz_path, int32_t first, int32_t n,
+                           int64_t batch_bytes, int threads, const uint8_t *pattern, int32_t pattern_len,
+                           ppg_cursor **out);
+int ppg_cursor_selected(const ppg_cursor *c, uint8_t **bytes, uint32_t **desc, int64_t *records, int64_t *nbytes);
+int ppg_cursor_selected_index(const ppg_cursor *c, int64_t *sel_off, int64_t *recno, int64_t cap);
 
 /* ======================= multi-GPU DecompressAll (one process per GPU) =======================
  * BatchedFASTQ's fan-out (BatchedFASTQ.cs:62-77: a task per chunk) becomes a fan-out over GPUs:

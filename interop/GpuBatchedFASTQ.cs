@@ -9,7 +9,10 @@
 //    next MoveNext here; the reference invalidates it, Q9);
 //  * Count(): ppg_file_decompress_all on one GPU, or ppg_dist_decompress_all when the process is
 //    one rank of a multi-GPU job (GpuJob: the ranks' RCCL communicator);
-//  * a rank of a multi-GPU job enumerates its own share (ppg_partition's chunk range).
+//  * a rank of a multi-GPU job enumerates its own share (ppg_partition's chunk range);
+//  * Where(pattern): the records whose Sequence contains the pattern (the body of Benchmark/Naive.cs
+//    RunPattern's loop), searched and compacted on the GPU by ppg_cursor_open_select: only the hits
+//    cross PCIe, each in a managed array of its own.
 // (Source only: no .NET SDK in this image; tests/test_interop_cs.py checks the externs it uses.)
 using System;
 using System.Collections;
@@ -127,6 +130,65 @@ public sealed class GpuBatchedFASTQ : IEnumerable<FastqRecord>, IDisposable
         {
             PpGpu.ppg_cursor_close(cur);
         }
+    }
+
+    /// <summary>records.Where(r => r.Sequence.Contains(pattern)) (Benchmark/Naive.cs:168-179), in canonical
+    /// order: every batch is searched on the GPU and only its hits are brought to the host.  pattern: up to
+    /// 64 ASCII characters without '\n'; "" yields every record.</summary>
+    public IEnumerable<FastqRecord> Where(string pattern)
+    {
+        var (first, n) = ChunkRange();
+        nint cur = OpenSelect(first, n, System.Text.Encoding.ASCII.GetBytes(pattern));
+        try
+        {
+            while (true)
+            {
+                var recs = NextSelected(cur);
+                if (recs == null) yield break;
+                foreach (var r in recs) yield return r;
+            }
+        }
+        finally
+        {
+            PpGpu.ppg_cursor_close(cur);
+        }
+    }
+
+    private unsafe nint OpenSelect(int first, int n, byte[] pat)
+    {
+        nint cur;
+        fixed (byte* p = pat)
+            PpGpu.Check(PpGpu.ppg_cursor_open_select(_Ctx, _Ix, _Path, first, n, BatchBytes, _Threads, p, pat.Length,
+                                                     out cur));
+        return cur;
+    }
+
+    // The next batch's selected records, or null after the last batch.  A record's text is copied into a
+    // managed array of its own; its descriptor is relative to the record's first byte (start = 0).
+    private static unsafe FastqRecord[]? NextSelected(nint cur)
+    {
+        int rc = PpGpu.ppg_cursor_next(cur, out _);
+        if (rc == (int)ZResult.STREAM_END) return null;
+        PpGpu.Check(rc);
+        byte* bytes;
+        uint* desc;
+        PpGpu.Check(PpGpu.ppg_cursor_selected(cur, &bytes, &desc, out long nrec, out _));
+        var off = new long[nrec + 1];
+        fixed (long* o = off) PpGpu.Check(PpGpu.ppg_cursor_selected_index(cur, o, null, nrec));
+        var recs = new FastqRecord[nrec];
+        for (long i = 0; i < nrec; i++)
+        {
+            var text = new byte[off[i + 1] - off[i]];
+            new ReadOnlySpan<byte>(bytes + off[i], text.Length).CopyTo(text);
+            var raw = new Memory<byte>(text);
+            uint* d = desc + 4 * i;
+            recs[i] = new FastqRecord(null!,
+                raw.Slice(1, (int)(d[0] - 1)),
+                raw.Slice((int)d[0] + 1, (int)(d[1] - d[0] - 1)),
+                raw.Slice((int)d[1] + 2, (int)(d[2] - d[1] - 2)),
+                raw.Slice((int)d[2] + 1, (int)(d[3] - d[2] - 1)));
+        }
+        return recs;
     }
 
     // The chunks this enumerator streams: all of them, or (multi-GPU job) this rank's share

@@ -149,6 +149,16 @@ internal static unsafe class PpGpu
     [DllImport(Lib)] public static extern int ppg_shard_set_seqquery(nint shard, byte* pattern, int patternLen,
         uint* devHitMask, long recCap);
     [DllImport(Lib)] public static extern int ppg_shard_seqquery_ready(nint shard, long* chunkHits, void* result);
+    // record selection: the records a mask selects, compacted on the GPU (device pointers; a null mask
+    // with maskCap 0 selects every record)
+    [DllImport(Lib)] public static extern int ppg_shard_select_size(nint shard, uint* devMask, long maskCap,
+        out long records, out long bytes);
+    [DllImport(Lib)] public static extern int ppg_shard_select_records(nint shard, uint* devMask, long maskCap,
+        long* devRecno, long* devSelOff, uint* devDesc, long selCap, byte* devBytes, long byteCap, out long records,
+        out long bytes);
+    [DllImport(Lib)] public static extern int ppg_shard_set_select(nint shard, uint* devMask, long maskCap,
+        long* devRecno, long* devSelOff, uint* devDesc, long selCap, byte* devBytes, long byteCap);
+    [DllImport(Lib)] public static extern int ppg_shard_select_ready(nint shard, out long records, out long bytes);
     [DllImport(Lib)] public static extern int ppg_shard_counts_to_device(nint shard, long* devDst);
     [DllImport(Lib)] public static extern int ppg_shard_timing(nint shard, out float inflateMs, out float parseMs,
         out float totalMs);
@@ -170,6 +180,13 @@ internal static unsafe class PpGpu
     [DllImport(Lib)] public static extern int ppg_cursor_packed(nint cursor, uint** bases, uint** mask, byte** qual,
         uint** seqLen, out long totalBases);
     [DllImport(Lib)] public static extern int ppg_cursor_packed_offsets(nint cursor, long* seqOff, long cap);
+    // the filtered enumerator: batches of the records whose Sequence contains the pattern, selected on
+    // the GPU, in pinned host memory (descriptors relative to each record's first byte)
+    [DllImport(Lib)] public static extern int ppg_cursor_open_select(nint ctx, nint ix, string gzPath, int first, int n,
+        long batchBytes, int threads, byte* pattern, int patternLen, out nint cursor);
+    [DllImport(Lib)] public static extern int ppg_cursor_selected(nint cursor, byte** bytes, uint** desc,
+        out long records, out long nbytes);
+    [DllImport(Lib)] public static extern int ppg_cursor_selected_index(nint cursor, long* selOff, long* recno, long cap);
 
     // ---- multi-GPU DecompressAll: partition + count all-gather over RCCL inside the library ----
     [DllImport(Lib)] public static extern int ppg_comm_unique_id(byte* id /* 128 bytes */);

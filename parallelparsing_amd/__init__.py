@@ -592,6 +592,110 @@ class SeqQuery:
         return f"SeqQuery(records={self.records}, hits={self.hits}, bases={self.bases}, counts={self.counts})"
 
 
+class SelectedRecords:
+    """The records a mask selects (include/ppgpu.h "record selection"): `bytes` (uint8, the selected
+    records' text back to back), `sel_off` (int64, records + 1 offsets into it), `desc` (records x 4:
+    the newline positions relative to the record's own first byte) and `recno` (int64, the records'
+    numbers), with `records` and `nbytes` the counts in use.  The arrays are either CUDA tensors on
+    one device (uint8, int64, int32 views of the uint32 descriptors) or numpy arrays (uint8, int64,
+    uint32); record(i) and iteration read host arrays."""
+
+    def __init__(self, bytes, sel_off, desc, recno, records=None, nbytes=None):   # noqa: A002
+        self.bytes, self.sel_off, self.desc, self.recno = bytes, sel_off, desc, recno
+        self.records = int(records) if records is not None else int(recno.shape[0])
+        self.nbytes = int(nbytes) if nbytes is not None else int(bytes.shape[0])
+
+    @classmethod
+    def empty(cls, sel_cap, byte_cap, device=None):
+        """Buffers for sel_cap records of byte_cap bytes in all: CUDA tensors on `device` (an int or
+        torch.device), numpy arrays when device is None; no record in use."""
+        sel_cap, byte_cap = int(sel_cap), int(byte_cap)
+        if device is None:
+            return cls(np.zeros(byte_cap, np.uint8), np.zeros(sel_cap + 1, np.int64), np.zeros((sel_cap, 4), np.uint32),
+                       np.zeros(sel_cap, np.int64), 0, 0)
+        import torch
+        dev = torch.device("cuda", device) if isinstance(device, int) else torch.device(device)
+        # (an empty tensor has no address: a buffer of capacity 0 keeps one element behind it)
+        back = [torch.zeros(max(int(n), 1), dtype=dt, device=dev)
+                for n, dt in ((byte_cap, torch.uint8), (sel_cap + 1, torch.int64), (4 * sel_cap, torch.int32), (sel_cap, torch.int64))]
+        out = cls(back[0][:byte_cap], back[1], back[2][:4 * sel_cap].view(-1, 4), back[3][:sel_cap], 0, 0)
+        out._back = back
+        return out
+
+    @property
+    def on_device(self):
+        return hasattr(self.bytes, "data_ptr")
+
+    @property
+    def sel_cap(self):
+        return int(self.recno.shape[0])
+
+    @property
+    def byte_cap(self):
+        return int(self.bytes.shape[0])
+
+    def _check_device(self, what):
+        import torch
+        for t, dt in ((self.bytes, torch.uint8), (self.sel_off, torch.int64), (self.desc, torch.int32),
+                      (self.recno, torch.int64)):
+            if not (hasattr(t, "data_ptr") and t.is_cuda and t.dtype == dt and t.is_contiguous()):
+                raise ValueError(f"{what}: the buffers must be contiguous CUDA tensors (uint8, int64, int32 words)")
+        if self.sel_off.numel() != self.sel_cap + 1 or self.desc.numel() != 4 * self.sel_cap:
+            raise ValueError(f"{what}: buffer sizes do not agree (SelectedRecords.empty makes them)")
+
+    def _ptrs(self):
+        b, off, desc, recno = getattr(self, "_back", None) or (self.bytes, self.sel_off, self.desc, self.recno)
+        return (C.c_void_p(recno.data_ptr()), C.c_void_p(off.data_ptr()), C.c_void_p(desc.data_ptr()),
+                self.sel_cap, C.c_void_p(b.data_ptr()), self.byte_cap)
+
+    def to_host(self):
+        """The same selection as numpy arrays (a copy; uint32 descriptors), cut to its records and bytes."""
+        nr, nb = self.records, self.nbytes
+        if not self.on_device:
+            return SelectedRecords(np.array(self.bytes[:nb]), np.array(self.sel_off[:nr + 1]),
+                                   np.array(self.desc).reshape(-1, 4)[:nr].copy(), np.array(self.recno[:nr]), nr, nb)
+        desc = self.desc.reshape(-1, 4)[:nr].cpu().numpy().view(np.uint32).reshape(-1, 4)
+        return SelectedRecords(self.bytes[:nb].cpu().numpy(), self.sel_off[:nr + 1].cpu().numpy(), desc,
+                               self.recno[:nr].cpu().numpy(), nr, nb)
+
+    def record(self, i):
+        """Selected record i as a FastqRecord over this selection's bytes (host arrays)."""
+        if self.on_device:
+            raise ValueError("SelectedRecords: record() reads host arrays (to_host() first)")
+        if not 0 <= i < self.records:
+            raise IndexError(i)
+        a, e = int(self.sel_off[i]), int(self.sel_off[i + 1])
+        n1, n2, n3, n4 = (int(v) for v in self.desc[i])
+        return FastqRecord(self.bytes[a:e], 0, n1, n2, n3, n4)
+
+    def __len__(self):
+        return self.records
+
+    def __iter__(self):
+        for i in range(self.records):
+            yield self.record(i)
+
+    def __repr__(self):
+        return f"SelectedRecords(records={self.records}, nbytes={self.nbytes})"
+
+
+def _mask_arg(mask, what):
+    """(pointer argument, mask_cap, the tensor to keep alive) of a record mask: None (every record), a
+    SeqQuery made with a mask, or a contiguous int32 / uint32 CUDA tensor of hit-mask words."""
+    if mask is None:
+        return None, 0, None
+    if isinstance(mask, SeqQuery):
+        if mask.hit_mask is None:
+            raise ValueError(f"{what}: the SeqQuery was made without a mask")
+        mask = mask.hit_mask
+    import torch
+    if not (hasattr(mask, "data_ptr") and mask.is_cuda and mask.dtype in (torch.int32, torch.uint32) and mask.is_contiguous()):
+        raise ValueError(f"{what}: mask must be a SeqQuery with a mask or a contiguous int32 / uint32 CUDA tensor")
+    if mask.numel() == 0:
+        return None, 0, None
+    return C.c_void_p(mask.data_ptr()), 32 * mask.numel(), mask
+
+
 class Shard:
     """DecompressAll over index chunks [first, first+n) resident on one GPU (ppg_shard)."""
 
@@ -634,7 +738,8 @@ class Shard:
             self.dev.after_torch()
 
     def run(self):
-        hooked = getattr(self, "_seqpack", None) is not None or getattr(self, "_sq_mask", None) is not None
+        hooked = getattr(self, "_seqpack", None) is not None or getattr(self, "_sq_mask", None) is not None or \
+            getattr(self, "_select", None) is not None
         if self._on_device or hooked:
             self._torch_order()   # the caller may have rewritten comp (or the hooks' tensors) since the last run
         check(lib.ppg_shard_run(self._h), "DecompressAll")
@@ -786,6 +891,58 @@ class Shard:
         if lib.ppg_shard_seqquery_ready(self._h, _ptr(ch), C.byref(res)) != 1:
             return None
         return SeqQuery(res, ch, getattr(self, "_sq_mask", None))
+
+    def select_size(self, mask=None):
+        """(records, bytes) a selection by `mask` holds, after a run of any number of batches
+        (ppg_shard_select_size): the capacities its SelectedRecords needs.  mask: None (every record),
+        a SeqQuery made with mask=True, or an int32 / uint32 CUDA tensor of hit-mask words."""
+        ptr, cap, _ = _mask_arg(mask, "select_size")
+        self._torch_order()
+        rec, nb = C.c_int64(), C.c_int64()
+        check(lib.ppg_shard_select_size(self._h, ptr, cap, C.byref(rec), C.byref(nb)), "select_size")
+        return rec.value, nb.value
+
+    def select_records(self, mask=None, out=None):
+        """The records `mask` selects of a one-batch shard after its run (ppg_shard_select_records), as a
+        SelectedRecords of CUDA tensors on this device: into `out`, or into a new one sized by
+        select_size().  Ordered after torch's stream, complete on return."""
+        ptr, cap, _ = _mask_arg(mask, "select_records")
+        if out is None:
+            rec, nb = self.select_size(mask)
+            out = SelectedRecords.empty(rec, nb, self.dev.device)
+        out._check_device("select_records")
+        self.dev.after_torch()
+        rec, nb = C.c_int64(), C.c_int64()
+        check(lib.ppg_shard_select_records(self._h, ptr, cap, *out._ptrs(), C.byref(rec), C.byref(nb)), "select_records")
+        out.records, out.nbytes = rec.value, nb.value
+        return out
+
+    def set_select(self, mask=None, out=None):
+        """From the next run on, every output batch appends the records `mask` selects to `out` (a
+        SelectedRecords of CUDA tensors on this device, sized for the whole shard) while its output is
+        resident (ppg_shard_set_select): works for shards of any number of batches, and runs after a
+        set_seqquery hook that fills the same mask tensor; the result is `selected` after the run.
+        mask as in select_size; out=None turns the hook off."""
+        if out is None:
+            check(lib.ppg_shard_set_select(self._h, None, 0, None, None, None, 0, None, 0), "set_select")
+            self._select = None
+            return self
+        ptr, cap, keep = _mask_arg(mask, "set_select")
+        out._check_device("set_select")
+        self._select = (keep, out)   # kept alive while the library may read / write them
+        self.dev.after_torch()
+        check(lib.ppg_shard_set_select(self._h, ptr, cap, *out._ptrs()), "set_select")
+        return self
+
+    @property
+    def selected(self):
+        """The SelectedRecords of the last run's set_select hook, or None when that run did not complete one."""
+        rec, nb = C.c_int64(), C.c_int64()
+        sel = getattr(self, "_select", None)
+        if lib.ppg_shard_select_ready(self._h, C.byref(rec), C.byref(nb)) != 1 or sel is None:
+            return None
+        sel[1].records, sel[1].nbytes = rec.value, nb.value
+        return sel[1]
 
     def results(self):
         n = self.n
@@ -961,17 +1118,28 @@ class Cursor:
 
     packed=True opens the packed enumerator (ppg_cursor_open_packed): a batch then carries no text
     and no descriptors but Batch.packed, a host PackedReads over the pinned planes (with the quality
-    plane when quality=True), so a fraction of the bytes crosses PCIe."""
+    plane when quality=True), so a fraction of the bytes crosses PCIe.
+
+    pattern=b"..." opens the filtered enumerator (ppg_cursor_open_select; not with packed=True): every
+    batch is searched for the pattern on the GPU and carries only Batch.selected, a host SelectedRecords
+    of the records whose Sequence contains it (b"": every record); nrecords counts the records scanned."""
 
     def __init__(self, index, gzip_path, first=0, n=None, batch_bytes=1 << 30, threads=8, device=None,
-                 packed=False, quality=True):
+                 packed=False, quality=True, pattern=None):
+        if packed and pattern is not None:
+            raise ValueError("Cursor: packed=True and pattern= exclude each other")
         self.index = index
         self.dev = device or Device.default()
         if n is None:
             n = index.Count - 1 - first
         self.packed, self.quality = bool(packed), bool(quality)
+        self.select = pattern is not None
         h = C.c_void_p()
-        if packed:
+        if self.select:
+            pat, m = _pattern_arg(pattern)
+            check(lib.ppg_cursor_open_select(self.dev.handle, index.handle, os.fsencode(gzip_path), int(first), int(n),
+                                             int(batch_bytes), int(threads), pat, m, C.byref(h)), "ppg_cursor_open_select")
+        elif packed:
             check(lib.ppg_cursor_open_packed(self.dev.handle, index.handle, os.fsencode(gzip_path), int(first), int(n),
                                              int(batch_bytes), int(threads), 1 if quality else 0, C.byref(h)),
                   "ppg_cursor_open_packed")
@@ -1001,7 +1169,26 @@ class Cursor:
         if rc == PPG_STREAM_END:
             return None
         check(rc, "ppg_cursor_next")
-        return Batch(b, self.packed_reads(b.nrecords) if self.packed else None)
+        return Batch(b, self.packed_reads(b.nrecords) if self.packed else None,
+                     self.selected_records() if self.select else None)
+
+    def selected_records(self):
+        """The current batch's selection (ppg_cursor_selected / ppg_cursor_selected_index) as a host
+        SelectedRecords: bytes and desc are views of pinned memory, valid until the next batch; sel_off
+        (batch-relative) and recno (among the records this cursor hands out) are copies."""
+        pb, pd = C.c_void_p(), C.c_void_p()
+        rec, nb = C.c_int64(), C.c_int64()
+        check(lib.ppg_cursor_selected(self._h, C.byref(pb), C.byref(pd), C.byref(rec), C.byref(nb)), "ppg_cursor_selected")
+        nr, nb = rec.value, nb.value
+        off, recno = np.zeros(nr + 1, np.int64), np.zeros(max(nr, 1), np.int64)
+        check(lib.ppg_cursor_selected_index(self._h, _ptr(off), _ptr(recno), nr), "ppg_cursor_selected_index")
+
+        def view(p, ct, n):
+            if not n or not p.value:
+                return np.zeros(0, ct)
+            return np.ctypeslib.as_array(C.cast(p, C.POINTER(ct)), (n,))
+
+        return SelectedRecords(view(pb, C.c_uint8, nb), off, view(pd, C.c_uint32, 4 * nr).reshape(-1, 4), recno[:nr], nr, nb)
 
     def packed_reads(self, nrecords):
         """The current batch's planes (ppg_cursor_packed / ppg_cursor_packed_offsets) as a host
@@ -1033,15 +1220,17 @@ class Cursor:
 
 class Batch:
     """One ppg_batch: text (uint8), raw_off / rec_off (int64, nchunks + 1), desc (nrecords x 4).  A
-    packed cursor's batch has text = desc = None and `packed`, a host PackedReads."""
+    packed cursor's batch has text = desc = None and `packed`, a host PackedReads; a select cursor's
+    has text = desc = None and `selected`, a host SelectedRecords."""
 
-    def __init__(self, b, packed=None):
+    def __init__(self, b, packed=None, selected=None):
         self.first_chunk, self.nchunks = b.first_chunk, b.nchunks
         self.record_base, self.nrecords = b.record_base, b.nrecords
         self.raw_off = np.ctypeslib.as_array(b.raw_off, (b.nchunks + 1,))
         self.rec_off = np.ctypeslib.as_array(b.rec_off, (b.nchunks + 1,))
         self.packed = packed
-        if packed is not None or not b.text:
+        self.selected = selected
+        if packed is not None or selected is not None or not b.text:
             self.text = self.desc = None
             return
         nt = int(self.raw_off[-1])
@@ -1136,6 +1325,26 @@ class BatchedFASTQ:
             for b in cur:
                 for k in range(b.nchunks):
                     yield from records_from_descriptors(b.raw(k).tobytes(), b.records(k))
+        finally:
+            cur.close()
+
+    def Where(self, pattern):
+        """The records whose Sequence contains `pattern` (the body of Benchmark/Naive.cs RunPattern's
+        loop: foreach record, if record.Sequence.Contains(pattern)), in canonical order, through the
+        select cursor (ppg_cursor_open_select) over chunk_range(): searched and compacted on the GPU,
+        only the hits reach the host.  Each batch's bytes are copied out before the next one is
+        requested.  pattern as in CountPattern (None or b"": every record)."""
+        first, n = self.chunk_range()
+        cur = Cursor(self.index, self.gzip_path, first=first, n=n, batch_bytes=self.batch_bytes,
+                     threads=16 if self.enable_ssd_optimization else 8, device=self.dev,
+                     pattern=b"" if pattern is None else pattern)
+        try:
+            for b in cur:
+                sel = b.selected
+                raw = sel.bytes.tobytes()
+                off, desc = sel.sel_off.tolist(), sel.desc.tolist()
+                for i in range(sel.records):
+                    yield FastqRecord(raw[off[i]:off[i + 1]], 0, *desc[i])
         finally:
             cur.close()
 

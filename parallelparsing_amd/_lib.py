@@ -124,6 +124,13 @@ _SIGS = {
     "ppg_shard_query_seq": (C.c_int, [vp, vp, i32, vp, i64, vp, vp]),
     "ppg_shard_set_seqquery": (C.c_int, [vp, vp, i32, vp, i64]),
     "ppg_shard_seqquery_ready": (C.c_int, [vp, vp, vp]),
+    "ppg_shard_select_size": (C.c_int, [vp, vp, i64, P(i64), P(i64)]),
+    "ppg_shard_select_records": (C.c_int, [vp, vp, i64, vp, vp, vp, i64, vp, i64, P(i64), P(i64)]),
+    "ppg_shard_set_select": (C.c_int, [vp, vp, i64, vp, vp, vp, i64, vp, i64]),
+    "ppg_shard_select_ready": (C.c_int, [vp, P(i64), P(i64)]),
+    "ppg_cursor_open_select": (C.c_int, [vp, vp, C.c_char_p, i32, i32, i64, C.c_int, vp, i32, P(vp)]),
+    "ppg_cursor_selected": (C.c_int, [vp, P(vp), P(vp), P(i64), P(i64)]),
+    "ppg_cursor_selected_index": (C.c_int, [vp, vp, vp, i64]),
     "ppg_cursor_open_packed": (C.c_int, [vp, vp, C.c_char_p, i32, i32, i64, C.c_int, i32, P(vp)]),
     "ppg_cursor_packed": (C.c_int, [vp, P(vp), P(vp), P(vp), P(vp), P(i64)]),
     "ppg_cursor_packed_offsets": (C.c_int, [vp, vp, i64]),

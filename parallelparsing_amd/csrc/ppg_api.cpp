@@ -40,6 +40,10 @@ static bool seqquery_linked() {
     return seq_linked() && ppg_launch_seq_query && ppg_launch_seq_query_chunks && ppg_launch_seq_query_totals;
 }
 
+static bool select_linked() {
+    return ppg_launch_sel_count && ppg_launch_sel_scan && ppg_launch_sel_place && ppg_launch_sel_copy;
+}
+
 namespace {
 
 // Byte source read in FileStream.Read(input, 0, CHUNK) steps (Core.cs:41).
@@ -737,7 +741,7 @@ static void seqquery_outputs(const ppg_shard *sh, int64_t *chunk_hits, void *res
 }
 
 // m bytes of pattern (NULL: m = 0) as the kernel's argument; false for a length outside [0, 64] or a '\n'
-static bool seqquery_pattern(const uint8_t *pattern, int32_t m, PpgSeqPattern *pat) {
+bool seqquery_pattern(const uint8_t *pattern, int32_t m, PpgSeqPattern *pat) {
     if (m < 0 || m > 64 || (m > 0 && !pattern)) return false;
     memset(pat, 0, sizeof *pat);
     for (int32_t i = 0; i < m; i++) {
@@ -749,6 +753,64 @@ static bool seqquery_pattern(const uint8_t *pattern, int32_t m, PpgSeqPattern *p
 
 static bool seqquery_mask_ok(const uint32_t *mask, int64_t rec_cap) {
     return rec_cap >= 0 && rec_cap % 32 == 0 && ((uintptr_t)mask & 3) == 0 && (mask != nullptr || rec_cap == 0);
+}
+
+// ---- record selection (ppg_seqselect.hip) ----
+int shard_select_reserve(ppg_shard *sh, int64_t nchunks) {
+    HIPCHK(sh->sel_ccnt.alloc(2 * ((size_t)nchunks + 1)));
+    HIPCHK(sh->sel_cbase.alloc(2 * ((size_t)nchunks + 1)));
+    HIPCHK(sh->sel_host.alloc(16));
+    return PPG_OK;
+}
+
+int shard_select_sizes(ppg_shard *sh, int32_t b0, int32_t b1, const uint32_t *recs, const uint32_t *mask, int64_t bit0,
+                       int64_t *records, int64_t *bytes) {
+    hipStream_t s = shard_stream(sh);
+    const int nb = b1 - b0;
+    if (!select_linked()) return PPG_UNSUPPORTED;
+    if (int rc = shard_select_reserve(sh, std::max<int64_t>(nb, sh->n))) return rc;   // once: every batch fits
+    const size_t h = sh->sel_ccnt.n / 2;   // records in the first half, bytes in the second
+    HIPCHK(ppg_launch_sel_count(s, sh->res.p + b0, sh->info.p + b0, sh->base.p + b0, recs, mask, (uint64_t)bit0,
+                                sh->sel_ccnt.p, sh->sel_ccnt.p + h, nb));
+    HIPCHK(ppg_launch_sel_scan(s, sh->sel_ccnt.p, sh->sel_ccnt.p + h, sh->sel_cbase.p, sh->sel_cbase.p + h,
+                               (int64_t *)sh->sel_host.p, nb));
+    HIPCHK(hipStreamSynchronize(s));
+    *records = ((volatile int64_t *)sh->sel_host.p)[0];
+    *bytes = ((volatile int64_t *)sh->sel_host.p)[1];
+    return PPG_OK;
+}
+
+int shard_select_move(ppg_shard *sh, int32_t b0, int32_t b1, const uint32_t *recs, const uint32_t *mask, int64_t bit0,
+                      int64_t rec_lo, int64_t byte_lo, int64_t records, int64_t bytes, int64_t *recno, int64_t *sel_off,
+                      uint32_t *desc, uint8_t *dst) {
+    hipStream_t s = shard_stream(sh);
+    const int nb = b1 - b0;
+    if (!select_linked()) return PPG_UNSUPPORTED;
+    const size_t h = sh->sel_ccnt.n / 2;
+    HIPCHK(grow_buf(sh->sel_src, (size_t)records + 1));
+    HIPCHK(grow_buf(sh->sel_span, (size_t)((byte_lo + bytes) / kSelSpan - byte_lo / kSelSpan) + 2));
+    HIPCHK(ppg_launch_sel_place(s, sh->res.p + b0, sh->info.p + b0, sh->base.p + b0, recs, mask, (uint64_t)bit0,
+                                sh->sel_cbase.p, sh->sel_cbase.p + h, sh->out.p, sh->jobs.p + b0, sh->offs.p, sh->oref.p + b0,
+                                rec_lo, byte_lo, recno, sel_off, desc, sh->sel_src.p, sh->sel_span.p, nb));
+    HIPCHK(ppg_launch_sel_copy(s, sel_off, sh->sel_src.p, sh->sel_span.p, rec_lo, rec_lo + records, byte_lo, byte_lo + bytes,
+                               dst));
+    return PPG_OK;
+}
+
+// batch_collect's hook, the last of a batch's hooks: the batch's selected records are appended
+static int select_hook(ppg_shard *sh, int32_t b0, int32_t b1, int64_t tot) {
+    if (b0 == 0) sh->sel_records = sh->sel_nbytes = 0;   // the run's first batch
+    if (sh->sel_mask && sh->total_records + tot > sh->sel_mask_cap) return PPG_BUF_ERROR;
+    const uint32_t *recs = sh->recs.p + 4 * (uint64_t)sh->total_records;
+    int64_t S = 0, B = 0;
+    if (int rc = shard_select_sizes(sh, b0, b1, recs, sh->sel_mask, sh->total_records, &S, &B)) return rc;
+    if (sh->sel_records + S > sh->sel_cap || sh->sel_nbytes + B > sh->sel_byte_cap) return PPG_BUF_ERROR;
+    if (int rc = shard_select_move(sh, b0, b1, recs, sh->sel_mask, sh->total_records, sh->sel_records, sh->sel_nbytes, S, B,
+                                   sh->sel_recno, sh->sel_off, sh->sel_desc, sh->sel_bytes))
+        return rc;
+    sh->sel_records += S;
+    sh->sel_nbytes += B;
+    return PPG_OK;
 }
 
 // Enqueue one batch [b0, b1) on the shard's stream, with no host synchronisation: inflate (+ the
@@ -842,6 +904,10 @@ int batch_collect(ppg_shard *sh, int32_t b0, int32_t b1, float &total_ms) {
                                      sh->sq_mask, b0 == 0))
             return rc;
     }
+    // selection of the batch's records, likewise and last: a query hook has filled this batch's bits
+    // of a mask the two share (ppg_shard_set_select)
+    if (sh->sel_on)
+        if (int rc = select_hook(sh, b0, b1, (int64_t)tot)) return rc;
     sh->t_inflate += a;
     sh->t_parse += b + c;
     total_ms += a + b + c;
@@ -891,10 +957,12 @@ int ppg_shard_run(ppg_shard *sh) {
     sh->keys_written = 0;
     sh->sp_written = 0;
     sh->sq_written = 0;
+    sh->sel_written = 0;
     sh->last_rc = shard_run(sh);
     sh->keys_written = sh->last_rc == PPG_OK && sh->keys_dev != nullptr;
     sh->sp_written = sh->last_rc == PPG_OK && sh->sp_off != nullptr;
     sh->sq_written = sh->last_rc == PPG_OK && sh->sq_on;
+    sh->sel_written = sh->last_rc == PPG_OK && sh->sel_on;
     return sh->last_rc;
 }
 
@@ -1217,6 +1285,158 @@ int ppg_shard_seqquery_ready(ppg_shard *sh, int64_t *chunk_hits, void *result) {
     if (!sh->sq_written) return 0;
     seqquery_outputs(sh, chunk_hits, result);
     return 1;
+}
+
+// ---- record selection: the sequence queries entry points' counterparts ----
+static bool select_bufs_ok(const int64_t *recno, const int64_t *sel_off, const uint32_t *desc, int64_t sel_cap,
+                           const uint8_t *bytes, int64_t byte_cap) {
+    // a descriptor is stored as one 16-B word, the text in 16-B words
+    return recno && sel_off && desc && bytes && sel_cap >= 0 && byte_cap >= 0 && ((uintptr_t)recno & 7) == 0 &&
+           ((uintptr_t)sel_off & 7) == 0 && ((uintptr_t)desc & 15) == 0 && ((uintptr_t)bytes & 15) == 0;
+}
+
+int ppg_shard_select_size(ppg_shard *sh, const uint32_t *dev_mask, int64_t mask_cap, int64_t *records, int64_t *bytes) {
+    if (!sh || !sh->ran || !seqquery_mask_ok(dev_mask, mask_cap)) return PPG_ARG_ERROR;
+    if (!select_linked()) return PPG_UNSUPPORTED;
+    if (dev_mask && sh->total_records > mask_cap) return PPG_BUF_ERROR;
+    HIPCHK(hipSetDevice(sh->ctx->device));
+    hipStream_t s = shard_stream(sh);
+    if (int rc = shard_select_reserve(sh, sh->n)) return rc;
+    const size_t h = sh->sel_ccnt.n / 2;
+    // every batch's descriptors are resident, each with record bases relative to its own first record
+    for (auto [b0, b1] : sh->batches) {
+        const uint64_t r0 = (uint64_t)sh->h_base[(size_t)b0];
+        HIPCHK(ppg_launch_sel_count(s, sh->res.p + b0, sh->info.p + b0, sh->base.p + b0, sh->recs.p + 4 * r0, dev_mask, r0,
+                                    sh->sel_ccnt.p + b0, sh->sel_ccnt.p + h + b0, b1 - b0));
+    }
+    HIPCHK(ppg_launch_sel_scan(s, sh->sel_ccnt.p, sh->sel_ccnt.p + h, sh->sel_cbase.p, sh->sel_cbase.p + h,
+                               (int64_t *)sh->sel_host.p, sh->batches.empty() ? 0 : sh->n));
+    HIPCHK(hipStreamSynchronize(s));
+    if (records) *records = ((volatile int64_t *)sh->sel_host.p)[0];
+    if (bytes) *bytes = ((volatile int64_t *)sh->sel_host.p)[1];
+    return PPG_OK;
+}
+
+int ppg_shard_select_records(ppg_shard *sh, const uint32_t *dev_mask, int64_t mask_cap, int64_t *dev_recno,
+                             int64_t *dev_sel_off, uint32_t *dev_desc, int64_t sel_cap, uint8_t *dev_bytes,
+                             int64_t byte_cap, int64_t *records, int64_t *bytes) {
+    if (!sh || !sh->ran || sh->batches.size() != 1 || !seqquery_mask_ok(dev_mask, mask_cap) ||
+        !select_bufs_ok(dev_recno, dev_sel_off, dev_desc, sel_cap, dev_bytes, byte_cap))
+        return PPG_ARG_ERROR;
+    if (!select_linked()) return PPG_UNSUPPORTED;
+    if (dev_mask && sh->total_records > mask_cap) return PPG_BUF_ERROR;
+    HIPCHK(hipSetDevice(sh->ctx->device));
+    int64_t S = 0, B = 0;
+    if (int rc = shard_select_sizes(sh, 0, sh->n, sh->recs.p, dev_mask, 0, &S, &B)) return rc;
+    if (records) *records = S;
+    if (bytes) *bytes = B;
+    if (S > sel_cap || B > byte_cap) return PPG_BUF_ERROR;   // before the movers: nothing is written
+    if (int rc = shard_select_move(sh, 0, sh->n, sh->recs.p, dev_mask, 0, 0, 0, S, B, dev_recno, dev_sel_off, dev_desc,
+                                   dev_bytes))
+        return rc;
+    HIPCHK(hipStreamSynchronize(shard_stream(sh)));
+    return PPG_OK;
+}
+
+int ppg_shard_set_select(ppg_shard *sh, const uint32_t *dev_mask, int64_t mask_cap, int64_t *dev_recno,
+                         int64_t *dev_sel_off, uint32_t *dev_desc, int64_t sel_cap, uint8_t *dev_bytes, int64_t byte_cap) {
+    if (!sh) return PPG_ARG_ERROR;
+    const bool off = !dev_mask && !mask_cap && !dev_recno && !dev_sel_off && !dev_desc && !sel_cap && !dev_bytes && !byte_cap;
+    if (!off && (!seqquery_mask_ok(dev_mask, mask_cap) ||
+                 !select_bufs_ok(dev_recno, dev_sel_off, dev_desc, sel_cap, dev_bytes, byte_cap)))
+        return PPG_ARG_ERROR;
+    sh->sel_on = off ? 0 : 1;
+    sh->sel_mask = dev_mask;
+    sh->sel_mask_cap = mask_cap;
+    sh->sel_recno = dev_recno;
+    sh->sel_off = dev_sel_off;
+    sh->sel_desc = dev_desc;
+    sh->sel_bytes = dev_bytes;
+    sh->sel_cap = sel_cap;
+    sh->sel_byte_cap = byte_cap;
+    sh->sel_written = 0;   // completed by the next run, not by an earlier one
+    return PPG_OK;
+}
+
+int ppg_shard_select_ready(ppg_shard *sh, int64_t *records, int64_t *bytes) {
+    if (!sh) return PPG_ARG_ERROR;
+    if (!sh->sel_written) return 0;
+    if (records) *records = sh->sel_records;
+    if (bytes) *bytes = sh->sel_nbytes;
+    return 1;
+}
+
+// Measurement hook of tools/seqselect_probe.py (not part of the ABI: no declaration in ppgpu.h).  On a
+// one-batch shard after its run, device time by hipEvents on the shard's stream, the median of reps
+// launches after one warm-up each, into ms[0..4]: count, scan, place, copy, and ppg_pack_raw of the same
+// batch (which moves every text byte once, as a selection of every record does); sizes[0..2]: the
+// selected records, their bytes and the raw text's bytes.  The buffers are the hook's own.
+int ppgx_seqselect_times(ppg_shard *sh, const uint32_t *dev_mask, int64_t mask_cap, int reps, float *ms, int64_t *sizes) {
+    if (!sh || !sh->ran || sh->batches.size() != 1 || !ms || !sizes || reps < 1 || !seqquery_mask_ok(dev_mask, mask_cap) ||
+        (dev_mask && sh->total_records > mask_cap))
+        return PPG_ARG_ERROR;
+    HIPCHK(hipSetDevice(sh->ctx->device));
+    hipStream_t s = shard_stream(sh);
+    int64_t S = 0, B = 0;
+    if (int rc = shard_select_sizes(sh, 0, sh->n, sh->recs.p, dev_mask, 0, &S, &B)) return rc;
+    std::vector<int64_t> raw_off((size_t)sh->n + 1, 0);
+    for (int32_t k = 0; k < sh->n; k++)
+        raw_off[(size_t)k + 1] = raw_off[(size_t)k] + (int64_t)sh->h_jobs[(size_t)k].raw_shift + (int64_t)sh->h_res[(size_t)k].produced;
+    DevBuf<int64_t> recno, off, draw;
+    DevBuf<uint32_t> desc;
+    DevBuf<uint8_t> dst, text;
+    HIPCHK(recno.alloc((size_t)S));
+    HIPCHK(off.alloc((size_t)S + 1));
+    HIPCHK(desc.alloc(4 * (size_t)S));
+    HIPCHK(dst.alloc((size_t)B + 16));
+    HIPCHK(text.alloc((size_t)raw_off[(size_t)sh->n]));
+    HIPCHK(draw.alloc(raw_off.size()));
+    HIPCHK(hipMemcpyAsync(draw.p, raw_off.data(), 8 * raw_off.size(), hipMemcpyHostToDevice, s));
+    // one whole move first: it sizes the scratch and leaves sel_off / the scratch in place for the copy
+    if (int rc = shard_select_move(sh, 0, sh->n, sh->recs.p, dev_mask, 0, 0, 0, S, B, recno.p, off.p, desc.p, dst.p)) return rc;
+    HIPCHK(hipStreamSynchronize(s));
+    const size_t h = sh->sel_ccnt.n / 2;
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    HIPCHK(hipEventCreate(&e0));
+    HIPCHK(hipEventCreate(&e1));
+    int rc = PPG_OK;
+    for (int what = 0; what < 5 && rc == PPG_OK; what++) {
+        std::vector<float> t;
+        for (int r = 0; r <= reps && rc == PPG_OK; r++) {
+            hipError_t e = hipEventRecord(e0, s);
+            if (e == hipSuccess && what == 0) {
+                e = ppg_launch_sel_count(s, sh->res.p, sh->info.p, sh->base.p, sh->recs.p, dev_mask, 0, sh->sel_ccnt.p,
+                                         sh->sel_ccnt.p + h, sh->n);
+            } else if (e == hipSuccess && what == 1) {
+                e = ppg_launch_sel_scan(s, sh->sel_ccnt.p, sh->sel_ccnt.p + h, sh->sel_cbase.p, sh->sel_cbase.p + h,
+                                        (int64_t *)sh->sel_host.p, sh->n);
+            } else if (e == hipSuccess && what == 2) {
+                e = ppg_launch_sel_place(s, sh->res.p, sh->info.p, sh->base.p, sh->recs.p, dev_mask, 0, sh->sel_cbase.p,
+                                         sh->sel_cbase.p + h, sh->out.p, sh->jobs.p, sh->offs.p, sh->oref.p, 0, 0, recno.p, off.p,
+                                         desc.p, sh->sel_src.p, sh->sel_span.p, sh->n);
+            } else if (e == hipSuccess && what == 3) {
+                e = ppg_launch_sel_copy(s, off.p, sh->sel_src.p, sh->sel_span.p, 0, S, 0, B, dst.p);
+            } else if (e == hipSuccess) {
+                e = ppg_launch_pack_raw(s, sh->out.p, sh->jobs.p, sh->res.p, sh->offs.p, sh->oref.p, draw.p, text.p, sh->n, 0);
+            }
+            if (e == hipSuccess) e = hipEventRecord(e1, s);
+            if (e == hipSuccess) e = hipEventSynchronize(e1);
+            float v = 0;
+            if (e == hipSuccess) e = hipEventElapsedTime(&v, e0, e1);
+            if (e != hipSuccess) rc = PPG_DEVICE_ERROR;
+            if (r) t.push_back(v);   // (r = 0 warms up)
+        }
+        if (rc == PPG_OK) {
+            std::sort(t.begin(), t.end());
+            ms[what] = t[t.size() / 2];
+        }
+    }
+    (void)hipEventDestroy(e0);
+    (void)hipEventDestroy(e1);
+    sizes[0] = S;
+    sizes[1] = B;
+    sizes[2] = raw_off[(size_t)sh->n];
+    return rc;
 }
 
 // Measurement hook of tools/seqpack_probe.py (not part of the ABI: no declaration in ppgpu.h).  On a

@@ -26,6 +26,12 @@
 // derived from the formats, ~232 B per 150 bp record with qualities and ~72 B without, against
 // 401 B of text + descriptors.  ppg_pack_raw, the text copy and the descriptor copy are skipped.
 //
+// A select cursor (ppg_cursor_open_select) goes further for a consumer that wants only the records a
+// pattern hits: the batch is queried on the device (ppg_seqquery.hip), the hits are compacted there
+// (ppg_seqselect.hip) and only they -- text, rebased descriptors, offsets and record numbers -- cross
+// PCIe.  The device side of a slot is bounded by the batch's text (every record may hit); the pinned
+// side starts small and grows to what the count pass reports before the copy.
+//
 // A batch stays valid until the next ppg_cursor_next call (the reference's records are likewise
 // invalid after the next MoveNext, BatchedFASTQ.cs:56 / SURVEY Q9).  Order is canonical (chunk 0's
 // records, then chunk 1's, ...), not the reference's interleaving.
@@ -57,6 +63,13 @@ struct Slot {
     DevBuf<uint8_t> dqual;
     PinnedBuf hseq_off, hseq_len, hbases, hmask, hqual;
     int64_t seq_total = 0;              // the batch's padded bases
+    // a select cursor's batch (ppg_cursor_open_select): the hit mask and the selection on the device,
+    // then the selection pinned
+    DevBuf<uint32_t> dsel_mask, dsel_desc;
+    DevBuf<int64_t> dsel_recno, dsel_off;
+    DevBuf<uint8_t> dsel_bytes;
+    PinnedBuf hsel_recno, hsel_off, hsel_desc, hsel_bytes;
+    int64_t sel_records = 0, sel_nbytes = 0;
     int32_t b0 = 0, b1 = 0;             // chunks [b0, b1) relative to the cursor's first
     int64_t nrec = 0;
     int rc = PPG_OK;
@@ -96,7 +109,11 @@ struct ppg_cursor {
     int pack_blocks = 256;              // pack = 2: workgroups of the pack kernels (PPG_CURSOR_PACK_BLOCKS)
     bool packed = false;                // batches carry packed reads instead of text + descriptors
     bool quality = false;               // ... with the quality plane
-    const Slot *cur = nullptr;          // the batch handed out last (the packed accessors read it)
+    bool select = false;                // batches carry the records whose Sequence contains pat
+    PpgSeqPattern pat = {};
+    int32_t pat_m = 0;
+    const Slot *cur = nullptr;          // the batch handed out last (the packed / selected accessors read it)
+    int64_t cur_base = 0;               // ... and its record_base
     int64_t pk_rec = 0, pk_bases = 0;   // packed slots: records / padded bases they are sized for at open
     bool verbose = false;               // PPG_CURSOR_VERBOSE: per-batch stage times on stderr
     std::chrono::steady_clock::time_point t_open = std::chrono::steady_clock::now();
@@ -170,9 +187,16 @@ struct ppg_cursor {
         pk_rec = rmax / 64 + 4096;
         pk_bases = (rmax / 2 + 31 * pk_rec + 31) / 32 * 32;
         const double pk_bytes = (double)pk_bases * (quality ? 1.375 : 0.375) + 12.0 * (double)pk_rec;
-        const double host_slot = (double)cmax + (packed ? pk_bytes : (double)rmax * 1.125);
-        const double dev_slot = (double)cmax + (packed ? (double)rmax * 1.4 + pk_bytes
-                                                       : (double)rmax * (pack == 1 ? 2.4 : 1.4));
+        // a select slot: the selection buffers for the whole batch's text on the device, the scratch of the
+        // query and the selection (~40 B per record); pinned, what batches select: unknown before the first
+        // count pass unless every record is selected (no pattern), which is the whole text
+        const bool select_all = select && pat_m == 0;
+        // (pin_select: the text, and 32 B of descriptor, record number and offset per record)
+        const double sel_pinned = select_all ? (double)rmax + 32.0 * (double)pk_rec : (double)(256 << 10) + 32.0 * 1024;
+        const double host_slot = (double)cmax + (packed ? pk_bytes : select ? sel_pinned : (double)rmax * 1.125);
+        const double dev_slot = (double)cmax + (packed   ? (double)rmax * 1.4 + pk_bytes
+                                                : select ? (double)rmax * 2.4 + 72.0 * (double)pk_rec
+                                                         : (double)rmax * (pack == 1 ? 2.4 : 1.4));
         size_t dfree = 0, dtotal = 0;
         const double havail = host_mem_available();
         if (hipMemGetInfo(&dfree, &dtotal) != hipSuccess) dfree = 0;
@@ -186,6 +210,13 @@ struct ppg_cursor {
             if (packed) {
                 if (int rc = grow_packed(s, pk_rec, pk_bases)) return rc;
                 if (int rc = shard_seq_reserve(&s.sh, max_chunks)) return rc;
+            } else if (select) {
+                HIPCHK(s.dsel_bytes.alloc((size_t)rmax + 16));
+                if (int rc = grow_select(s, pk_rec)) return rc;
+                if (int rc = shard_seq_reserve(&s.sh, max_chunks)) return rc;
+                if (int rc = shard_select_reserve(&s.sh, max_chunks)) return rc;
+                // (a pinned buffer that grows does so in a worker, inside the pipeline: not where its size is known)
+                if (int rc = select_all ? pin_select(s, pk_rec, rmax) : pin_select(s, 1024, 256 << 10)) return rc;
             } else {
                 HIPCHK(s.text.alloc((size_t)rmax));
                 if (pack) HIPCHK(s.draw_off.alloc((size_t)max_chunks + 1));
@@ -213,6 +244,24 @@ struct ppg_cursor {
             HIPCHK(s.dqual.alloc((size_t)bases));
             HIPCHK(s.hqual.alloc((size_t)bases));
         }
+        return PPG_OK;
+    }
+
+    // a select slot's device buffers for nrec records of the batch (its text is bounded at open)
+    int grow_select(Slot &s, int64_t nrec) {
+        HIPCHK(s.dsel_mask.alloc((size_t)nrec / 32 + 1));
+        HIPCHK(s.dsel_recno.alloc((size_t)nrec));
+        HIPCHK(s.dsel_off.alloc((size_t)nrec + 1));
+        HIPCHK(s.dsel_desc.alloc(4 * (size_t)nrec + 4));
+        return PPG_OK;
+    }
+
+    // ... and its pinned side for nrec selected records of nbytes bytes
+    int pin_select(Slot &s, int64_t nrec, int64_t nbytes) {
+        HIPCHK(s.hsel_recno.alloc(8 * (size_t)nrec));
+        HIPCHK(s.hsel_off.alloc(8 * ((size_t)nrec + 1)));
+        HIPCHK(s.hsel_desc.alloc(16 * (size_t)nrec));
+        HIPCHK(s.hsel_bytes.alloc((size_t)nbytes));
         return PPG_OK;
     }
 
@@ -256,7 +305,7 @@ struct ppg_cursor {
         for (int32_t k = 0; k < m; k++)
             s.raw_off[(size_t)k + 1] = s.raw_off[(size_t)k] + (int64_t)P[(size_t)a + k].offset.size() +
                                        (int64_t)s.sh.h_res[(size_t)k].produced;
-        if (!packed && (size_t)s.raw_off[(size_t)m] > s.text.n) return PPG_BUF_ERROR;  // produced <= Output span: never
+        if (!packed && !select && (size_t)s.raw_off[(size_t)m] > s.text.n) return PPG_BUF_ERROR;  // produced <= Output span: never
         s.nrec = s.sh.total_records;
         if (packed) {
             // layout and pack while the batch is resident; only the planes cross PCIe
@@ -284,6 +333,43 @@ struct ppg_cursor {
                                 "%.1f, total %.1f ms\n", i, m,
                         std::chrono::duration<double, std::milli>(t0 - t_open).count(), tw, tr - tw, tp - tr, td - tp,
                         (double)kms, th - td, ms() - th, ms());
+            s.rec_off.assign((size_t)m + 1, 0);
+            for (int32_t k = 0; k < m; k++)
+                s.rec_off[(size_t)k + 1] = s.sh.h_base[(size_t)k] + (int64_t)s.sh.h_info[(size_t)k].records;
+            return PPG_OK;
+        }
+        if (select) {
+            // query and select while the batch is resident; only the selection crosses PCIe
+            if ((size_t)s.nrec + 1 > s.dsel_off.n)
+                if (int rc = grow_select(s, s.nrec + s.nrec / 4)) return rc;
+            if (int rc = shard_seq_query(&s.sh, 0, m, s.sh.recs.p, 0, s.nrec, pat, pat_m, s.dsel_mask.p, true)) return rc;
+            if (int rc = shard_select_sizes(&s.sh, 0, m, s.sh.recs.p, s.dsel_mask.p, 0, &s.sel_records, &s.sel_nbytes))
+                return rc;
+            if ((size_t)s.sel_nbytes + 16 > s.dsel_bytes.n) return PPG_BUF_ERROR;   // a selection is part of the text: never
+            if (8 * (size_t)s.sel_records > s.hsel_recno.n || (size_t)s.sel_nbytes > s.hsel_bytes.n)
+                if (int rc = pin_select(s, s.sel_records + s.sel_records / 4, s.sel_nbytes + s.sel_nbytes / 4)) return rc;
+            if (int rc = shard_select_move(&s.sh, 0, m, s.sh.recs.p, s.dsel_mask.p, 0, 0, 0, s.sel_records, s.sel_nbytes,
+                                           s.dsel_recno.p, s.dsel_off.p, s.dsel_desc.p, s.dsel_bytes.p))
+                return rc;
+            stage_wait(i, kHost);
+            const double th = ms();
+            const size_t nr = (size_t)s.sel_records;
+            HIPCHK(hipMemcpyAsync(s.hsel_off.p, s.dsel_off.p, 8 * (nr + 1), hipMemcpyDeviceToHost, st));
+            if (nr) {
+                HIPCHK(hipMemcpyAsync(s.hsel_recno.p, s.dsel_recno.p, 8 * nr, hipMemcpyDeviceToHost, st));
+                HIPCHK(hipMemcpyAsync(s.hsel_desc.p, s.dsel_desc.p, 16 * nr, hipMemcpyDeviceToHost, st));
+            }
+            if (s.sel_nbytes)
+                HIPCHK(hipMemcpyAsync(s.hsel_bytes.p, s.dsel_bytes.p, (size_t)s.sel_nbytes, hipMemcpyDeviceToHost, st));
+            HIPCHK(hipStreamSynchronize(st));
+            stage_done(i, kHost);
+            if (verbose)
+                fprintf(stderr, "[cursor] select batch %zu: %d chunks, started at %.1f ms: read wait %.1f, read %.1f, "
+                                "H2D+prepare %.1f, decode %.1f (kernels %.1f), query+select %.1f, host wait + to host %.1f, "
+                                "total %.1f ms; %lld of %lld records, %lld bytes\n", i, m,
+                        std::chrono::duration<double, std::milli>(t0 - t_open).count(), tw, tr - tw, tp - tr, td - tp,
+                        (double)kms, th - td, ms() - th, ms(), (long long)s.sel_records, (long long)s.nrec,
+                        (long long)s.sel_nbytes);
             s.rec_off.assign((size_t)m + 1, 0);
             for (int32_t k = 0; k < m; k++)
                 s.rec_off[(size_t)k + 1] = s.sh.h_base[(size_t)k] + (int64_t)s.sh.h_info[(size_t)k].records;
@@ -344,7 +430,8 @@ struct ppg_cursor {
 extern "C" {
 
 static int cursor_open(ppg_ctx *ctx, const ppg_index *ix, const char *gz_path, int32_t first, int32_t n,
-                       int64_t batch_bytes, int threads, bool packed, bool quality, ppg_cursor **out) {
+                       int64_t batch_bytes, int threads, bool packed, bool quality, const PpgSeqPattern *pat,
+                       int32_t pat_m, ppg_cursor **out) {
     if (!ctx || !ix || !gz_path || !out || first < 0 || n < 0 || (size_t)first + (size_t)n + 1 > ix->pts.size())
         return PPG_ARG_ERROR;
     if (int v = ppg_index_validate(ix, first, n)) return v;
@@ -358,6 +445,11 @@ static int cursor_open(ppg_ctx *ctx, const ppg_index *ix, const char *gz_path, i
     c->threads = threads > 0 ? threads : 8;
     c->packed = packed;
     c->quality = quality;
+    if (pat) {
+        c->select = true;
+        c->pat = *pat;
+        c->pat_m = pat_m;
+    }
     if (const char *e = getenv("PPG_CURSOR_SLOTS")) c->nslots = std::min(kMaxSlots, std::max(2, atoi(e)));
     if (const char *e = getenv("PPG_CURSOR_PACK")) c->pack = std::min(2, std::max(0, atoi(e)));
     if (const char *e = getenv("PPG_CURSOR_PACK_BLOCKS")) c->pack_blocks = std::max(4, atoi(e));
@@ -399,13 +491,13 @@ static int cursor_open(ppg_ctx *ctx, const ppg_index *ix, const char *gz_path, i
 
 int ppg_cursor_open(ppg_ctx *ctx, const ppg_index *ix, const char *gz_path, int32_t first, int32_t n,
                     int64_t batch_bytes, int threads, ppg_cursor **out) {
-    return cursor_open(ctx, ix, gz_path, first, n, batch_bytes, threads, false, false, out);
+    return cursor_open(ctx, ix, gz_path, first, n, batch_bytes, threads, false, false, nullptr, 0, out);
 }
 
 int ppg_cursor_open_packed(ppg_ctx *ctx, const ppg_index *ix, const char *gz_path, int32_t first, int32_t n,
                            int64_t batch_bytes, int threads, int32_t planes, ppg_cursor **out) {
     if (planes & ~1) return PPG_ARG_ERROR;
-    return cursor_open(ctx, ix, gz_path, first, n, batch_bytes, threads, true, (planes & 1) != 0, out);
+    return cursor_open(ctx, ix, gz_path, first, n, batch_bytes, threads, true, (planes & 1) != 0, nullptr, 0, out);
 }
 
 int ppg_cursor_packed(const ppg_cursor *c, uint32_t **bases, uint32_t **mask, uint8_t **qual, uint32_t **seq_len,
@@ -428,6 +520,36 @@ int ppg_cursor_packed_offsets(const ppg_cursor *c, int64_t *seq_off, int64_t cap
     return PPG_OK;
 }
 
+int ppg_cursor_open_select(ppg_ctx *ctx, const ppg_index *ix, const char *gz_path, int32_t first, int32_t n,
+                           int64_t batch_bytes, int threads, const uint8_t *pattern, int32_t pattern_len,
+                           ppg_cursor **out) {
+    PpgSeqPattern pat;
+    if (!seqquery_pattern(pattern, pattern_len, &pat)) return PPG_ARG_ERROR;
+    return cursor_open(ctx, ix, gz_path, first, n, batch_bytes, threads, false, false, &pat, pattern_len, out);
+}
+
+int ppg_cursor_selected(const ppg_cursor *c, uint8_t **bytes, uint32_t **desc, int64_t *records, int64_t *nbytes) {
+    if (!c || !c->select || !c->cur) return PPG_ARG_ERROR;
+    const Slot &s = *c->cur;
+    if (bytes) *bytes = s.hsel_bytes.p;
+    if (desc) *desc = (uint32_t *)s.hsel_desc.p;
+    if (records) *records = s.sel_records;
+    if (nbytes) *nbytes = s.sel_nbytes;
+    return PPG_OK;
+}
+
+int ppg_cursor_selected_index(const ppg_cursor *c, int64_t *sel_off, int64_t *recno, int64_t cap) {
+    if (!c || !c->select || !c->cur) return PPG_ARG_ERROR;
+    const Slot &s = *c->cur;
+    if (cap < s.sel_records) return PPG_BUF_ERROR;
+    if (sel_off) memcpy(sel_off, s.hsel_off.p, 8 * ((size_t)s.sel_records + 1));
+    if (recno) {
+        const int64_t *r = (const int64_t *)s.hsel_recno.p;
+        for (int64_t i = 0; i < s.sel_records; i++) recno[i] = c->cur_base + r[i];
+    }
+    return PPG_OK;
+}
+
 int ppg_cursor_next(ppg_cursor *c, ppg_batch *b) {
     if (!c || !b) return PPG_ARG_ERROR;
     if (c->next >= c->batches.size()) return PPG_STREAM_END;
@@ -445,10 +567,12 @@ int ppg_cursor_next(ppg_cursor *c, ppg_batch *b) {
     b->nchunks = s.b1 - s.b0;
     b->record_base = c->record_base;
     b->nrecords = s.nrec;
-    b->text = c->packed ? nullptr : s.text.p;
+    const bool no_text = c->packed || c->select;
+    b->text = no_text ? nullptr : s.text.p;
     b->raw_off = s.raw_off.data();
-    b->desc = c->packed ? nullptr : (const uint32_t *)s.desc.p;
+    b->desc = no_text ? nullptr : (const uint32_t *)s.desc.p;
     b->rec_off = s.rec_off.data();
+    c->cur_base = c->record_base;
     c->record_base += s.nrec;
     c->cur = &s;
     c->next++;

@@ -100,6 +100,19 @@ struct PpgSeqPattern {
     uint64_t w[8];
 };
 
+// ppg_sel_copy: the destination bytes one workgroup writes (256 threads x 4 words of 16 B); ppg_sel_place
+// records, per multiple of it inside a batch's destination range, the selected record that holds that byte
+constexpr uint32_t kSelSpan = 16384;
+
+// ppg_sel_place -> ppg_sel_copy, per selected record with first destination byte o (absolute in the
+// destination buffer) and text raw_k[a, ..): destination byte p comes from address fast + p when
+// p >= cend (the body part) and from slow + p below (the offset carry part)
+struct PpgSelSrc {
+    int64_t fast;   // (address of body_k) - |offset_k| + a - o
+    int64_t slow;   // (address of offset_k) + a - o
+    int64_t cend;   // o + |offset_k| - a
+};
+
 #define PPG_FLAG_NO_EOB 1     // the symbol after the last output byte is not end-of-block
 #define PPG_FLAG_OVERRUN 2    // decoding consumed bits past the chunk's compressed slice
 #define PPG_FLAG_BLK_FULL 16  // CreateIndex pass 1: more block ends than blk_cap

@@ -214,6 +214,21 @@ struct ppg_shard {
     DevBuf<uint32_t> sq_len, sq_bits;    // sq_bits: a batch's hit bits when the caller gives no mask
     DevBuf<uint64_t> sq_acc;             // records, hits, (unused), count[5] of the run so far
     PinnedBuf sq_host;                   // a ppg_seq_query_result, then hits per chunk: stored by the kernels
+    // ppg_shard_set_select: every batch's selected records are also appended to these buffers
+    // (ppg_seqselect.hip), output records and bytes continuing from the batches before
+    int sel_on = 0;
+    const uint32_t *sel_mask = nullptr;
+    int64_t sel_mask_cap = 0;
+    int64_t *sel_recno = nullptr, *sel_off = nullptr;
+    uint32_t *sel_desc = nullptr;
+    uint8_t *sel_bytes = nullptr;
+    int64_t sel_cap = 0, sel_byte_cap = 0;
+    int64_t sel_records = 0, sel_nbytes = 0;   // selected by the run's batches so far
+    int sel_written = 0;                       // the last successful run completed the selection (set by shard_run)
+    DevBuf<uint64_t> sel_ccnt, sel_cbase;      // per chunk: selected records, then their bytes; the scans of both
+    DevBuf<PpgSelSrc> sel_src;                 // scratch: where the bytes of a batch's selected records come from
+    DevBuf<int64_t> sel_span;                  // scratch: ppg_sel_place's span_first
+    PinnedBuf sel_host;                        // a batch's totals (records, bytes), stored by the kernel
     // split chunks (ppg_shard_set_split): the inflate launch runs sub-jobs, ppg_split_merge folds
     // them back into per-chunk results and census regions
     int32_t nsub = 0;                            // side points in use (0: one wave per chunk)
@@ -271,6 +286,17 @@ int shard_seq_pack(ppg_shard *sh, int32_t b0, int32_t b1, const uint32_t *recs, 
 // chunks' hits are in sq_host once the stream has drained.
 int shard_seq_query(ppg_shard *sh, int32_t b0, int32_t b1, const uint32_t *recs, int64_t rec0, int64_t tot,
                     const PpgSeqPattern &pat, int32_t m, uint32_t *mask, bool first);
+bool seqquery_pattern(const uint8_t *pattern, int32_t m, PpgSeqPattern *pat);
+// record selection of chunks [b0, b1) of one resident batch (recs: the batch's first descriptor; record j
+// of the batch has bit bit0 + j of mask, a null mask selects all).  sizes: the selected records and their
+// bytes (blocks on the shard's stream).  move: after sizes of the same chunks, queues the selection into
+// the buffers from output record rec_lo and byte byte_lo on; recno counts from bit0.
+int shard_select_reserve(ppg_shard *sh, int64_t nchunks);
+int shard_select_sizes(ppg_shard *sh, int32_t b0, int32_t b1, const uint32_t *recs, const uint32_t *mask, int64_t bit0,
+                       int64_t *records, int64_t *bytes);
+int shard_select_move(ppg_shard *sh, int32_t b0, int32_t b1, const uint32_t *recs, const uint32_t *mask, int64_t bit0,
+                      int64_t rec_lo, int64_t byte_lo, int64_t records, int64_t bytes, int64_t *recno, int64_t *sel_off,
+                      uint32_t *desc, uint8_t *dst);
 
 // collectives of a ppg_comm beyond the count gather (ppg_comm.cpp), used by ppg_pairs.hip
 int comm_size(const ppg_comm *c, int32_t *rank, int32_t *nranks);

@@ -90,3 +90,20 @@ PPG_WEAK hipError_t ppg_launch_seq_query_chunks(hipStream_t s, const PpgInflateR
                                                 const uint64_t *base, int m, uint32_t *hit_words, uint64_t rec0,
                                                 uint64_t *acc, int64_t *host_chunk_hits, int n);
 PPG_WEAK hipError_t ppg_launch_seq_query_totals(hipStream_t s, const uint64_t *acc, int64_t *host_result);
+
+// ---- ppg_seqselect.hip ----
+// Weak for the same reason (select_linked, ppg_api.cpp).
+PPG_WEAK hipError_t ppg_launch_sel_count(hipStream_t s, const PpgInflateResult *ires, const PpgParseInfo *info,
+                                         const uint64_t *base, const uint32_t *recs, const uint32_t *mask,
+                                         uint64_t bit0, uint64_t *crec, uint64_t *cbyte, int n);
+PPG_WEAK hipError_t ppg_launch_sel_scan(hipStream_t s, const uint64_t *crec, const uint64_t *cbyte, uint64_t *rbase,
+                                        uint64_t *bbase, int64_t *host_totals, int n);
+PPG_WEAK hipError_t ppg_launch_sel_place(hipStream_t s, const PpgInflateResult *ires, const PpgParseInfo *info,
+                                         const uint64_t *base, const uint32_t *recs, const uint32_t *mask,
+                                         uint64_t bit0, const uint64_t *rbase, const uint64_t *bbase, const uint8_t *out,
+                                         const PpgInflateJob *jobs, const uint8_t *offs, const PpgOffsetRef *oref,
+                                         int64_t rec_lo, int64_t byte_lo, int64_t *recno, int64_t *sel_off, uint32_t *desc,
+                                         PpgSelSrc *src, int64_t *span_first, int n);
+PPG_WEAK hipError_t ppg_launch_sel_copy(hipStream_t s, const int64_t *sel_off, const PpgSelSrc *src,
+                                        const int64_t *span_first, int64_t rec_lo, int64_t rec_hi, int64_t d0, int64_t d1,
+                                        uint8_t *dst);

@@ -25,6 +25,8 @@
 #                               (e.g. stamps:--share_8)                            -> stamps*.log
 #   chunkapi                    the per-chunk Decompress leg only ($CHUNK_ARGS)    -> chunkapi.json
 #   latency[:args]              tools/chunk_latency.py with every launch's phases  -> chunk_latency.txt
+#   seqselect[:args]            tools/seqselect_probe.py: selection kernels and the select cursor against
+#                               the text cursor -> profiles/seqselect_probe.json + seqselect_probe.log
 set -o pipefail
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT" || exit 1
 tag=$1; shift
@@ -110,6 +112,11 @@ run_step() {
   latency)
     PPG_CHUNK_VERBOSE=1 timeout -k 10 300 python3 -u tools/chunk_latency.py $xa > $O/chunk_latency.txt 2>&1 || { tail -5 $O/chunk_latency.txt; return 1; }
     grep -v PPG_CHUNK $O/chunk_latency.txt | tail -14 ;;
+  seqselect)
+    env ${SELECT_VERBOSE:+PPG_CURSOR_VERBOSE=1} timeout -k 10 500 python3 -u tools/seqselect_probe.py $xa \
+      > $O/seqselect_probe.out 2> $O/seqselect_probe.log || { tail -5 $O/seqselect_probe.log; return 1; }
+    cp profiles/seqselect_probe.json $O/
+    python3 -c "import json,sys; d=json.load(open(sys.argv[1])); print(json.dumps(d['kernels'])[:1500]); print({k: (round(v['records_per_s']/1e6,1), v['bytes_to_host']) for k, v in d['from_file'].items()})" $O/seqselect_probe.json ;;
   *)
     echo "gpu_run.sh: unknown step $step" >&2; return 2 ;;
   esac
