@@ -383,6 +383,82 @@ int ppg_shard_set_select(ppg_shard *sh, const uint32_t *dev_mask, int64_t mask_c
                          int64_t byte_cap);
 int ppg_shard_select_ready(ppg_shard *sh, int64_t *records, int64_t *bytes);
 
+/* ---- read filters: length, N content and quality per record, and the pass bit they give ----
+ * The step a FASTQ consumer runs first is quality control: drop the reads that are too short, hold too
+ * many N, have a low mean quality or too many low-quality bases.  The numbers come from the Sequence
+ * and Quality slices alone, so they are made on the GPU while the text is resident; the pass bits are
+ * a mask in the hit-mask format, which a selection above turns into the records themselves.
+ * For shard record j (numbered as above) with descriptor (n1,n2,n3,n4) relative to raw_k:
+ *   S_j      raw_k[n1+1, n2), L_j = n2 - n1 - 1: the Sequence slice of the packed reads and the queries
+ *            (a CRLF file's '\r' is part of it);
+ *   Q_j      raw_k[n3+1, n4), Lq_j = n4 - n3 - 1: the Quality slice itself, neither cut nor padded to L_j
+ *            (the packed reads' qual plane is);
+ *   other_j  the bytes of S_j that are none of 'A' 'C' 'G' 'T' (upper case): the popcount of the record's
+ *            bits in the packed reads' mask plane; its sum over the records is a query's count[4];
+ *   qsum_j   the sum of the bytes of Q_j as unsigned values, in 64 bits;
+ *   low_j    the bytes of Q_j whose unsigned value is < qual_base + low_q.
+ * A filter is a ppg_read_filter: eight int64_t, passed as const void * so that a binding passes its own
+ * struct's address.  criteria is a set of bits: PPG_FILTER_LENGTH 1, PPG_FILTER_OTHER 2, PPG_FILTER_MEAN 4,
+ * PPG_FILTER_LOW 8, PPG_FILTER_AND_MASK 0x100.  The criteria, in exact signed 64-bit integer arithmetic:
+ *   LENGTH   min_len <= L_j and (max_len < 0 or L_j <= max_len);
+ *   OTHER    other_j <= max_other;
+ *   MEAN     1000 * (qsum_j - qual_base * Lq_j) >= min_mean_milli * Lq_j   (true when Lq_j = 0);
+ *   LOW      1000 * low_j <= max_low_milli * Lq_j                          (true when Lq_j = 0).
+ * pass_j = chunk k's status is 0 and every enabled criterion holds.  A failed chunk contributes no
+ * passes, no bytes to the totals, and metrics rows of zeros, as in a query; records the reference
+ * parses twice count twice.  With none of the four criteria every record of a decoded chunk
+ * passes: metrics and totals alone.
+ * ppg_read_filter_check is host only: PPG_ARG_ERROR for a NULL filter, unknown criteria bits,
+ * min_len < 0, max_len < -1 or 0 <= max_len < min_len, OTHER with max_other < 0, qual_base outside
+ * [0, 255], low_q < 0 or qual_base + low_q > 256, max_low_milli outside [0, 1000], |min_mean_milli| >
+ * 255000; PPG_OK otherwise.  Every entry point below applies it.
+ * dev_pass_mask (optional): the hit-mask format, 4-byte aligned, rec_cap a multiple of 32.  Without
+ * AND_MASK it is written like a query's mask: every word below ceil(records / 32) whole, pad bits 0,
+ * nothing at or past rec_cap / 32.  With AND_MASK a mask is required, bit j of records [0, records)
+ * becomes old & pass_j and no other bit changes: one mask carries "pattern hit and passes" into a
+ * selection.  dev_metrics (optional): 8-byte aligned, metrics_cap rows of 24 bytes, row j = uint32 L_j,
+ * other_j, Lq_j, low_j, then uint64 qsum_j.  chunk_passed (optional): host int64[n], the passes per chunk.
+ * `result` (optional) points at a ppg_read_filter_result: failed[c] counts the records of decoded chunks
+ * that fail criterion c (LENGTH, OTHER, MEAN, LOW), each on its own, 0 for a disabled criterion;
+ * qual_count[v] is the number of Quality bytes of value v, so the sum of v * qual_count[v] is the sum
+ * of qsum_j.  records > rec_cap (with a mask) or > metrics_cap (with metrics): PPG_BUF_ERROR, nothing
+ * written.  Every output is a function of the text and the filter alone.
+ *  ppg_shard_filter_reads      a one-batch shard after its run, blocking; PPG_ARG_ERROR as for
+ *                              ppg_shard_query_seq, for a bad filter, mask, metrics pointer or cap.
+ *  ppg_shard_set_readfilter    any number of batches: from the next run on every batch is measured
+ *                              while its output is resident, record numbers and totals carried across
+ *                              batches.  The filter is copied at the call; a NULL filter turns it off.
+ *                              A batch's hooks run in the order keys, pack, query, filter, select: a
+ *                              filter with AND_MASK on the query hook's mask sees this batch's hit
+ *                              bits, and the select hook sees the product.  A run with more records
+ *                              than a cap fails with PPG_BUF_ERROR.
+ *  ppg_shard_readfilter_ready  as ppg_shard_seqquery_ready. */
+typedef struct {
+    int64_t criteria;        /* PPG_FILTER_* bits */
+    int64_t min_len;
+    int64_t max_len;         /* -1: no upper bound */
+    int64_t max_other;
+    int64_t qual_base;       /* the Quality byte of quality 0 (33 for Sanger / Illumina 1.8+) */
+    int64_t min_mean_milli;  /* 1000 x the least mean quality */
+    int64_t low_q;           /* a base is low when its quality is below this */
+    int64_t max_low_milli;   /* 1000 x the largest fraction of low bases */
+} ppg_read_filter;
+typedef struct {
+    int64_t records;         /* records measured */
+    int64_t passed;
+    int64_t failed[4];       /* LENGTH, OTHER, MEAN, LOW */
+    int64_t bases;           /* sum of L_j */
+    int64_t other;           /* sum of other_j */
+    int64_t qual_bytes;      /* sum of Lq_j */
+    int64_t qual_count[256];
+} ppg_read_filter_result;
+int ppg_read_filter_check(const void *filter);
+int ppg_shard_filter_reads(ppg_shard *sh, const void *filter, uint32_t *dev_pass_mask, int64_t rec_cap,
+                           void *dev_metrics, int64_t metrics_cap, int64_t *chunk_passed, void *result);
+int ppg_shard_set_readfilter(ppg_shard *sh, const void *filter, uint32_t *dev_pass_mask, int64_t rec_cap,
+                             void *dev_metrics, int64_t metrics_cap);
+int ppg_shard_readfilter_ready(ppg_shard *sh, int64_t *chunk_passed, void *result);
+
 /* Device-resident per-chunk record counts (int64[n]) copied to caller device memory on this
  * GPU (the input of the cross-GPU all-gather). */
 int ppg_shard_counts_to_device(ppg_shard *sh, int64_t *dev_dst);
@@ -479,6 +555,20 @@ int ppg_cursor_open_select(ppg_ctx *ctx, const ppg_index *ix, const char *gz_pat
                            ppg_cursor **out);
 int ppg_cursor_selected(const ppg_cursor *c, uint8_t **bytes, uint32_t **desc, int64_t *records, int64_t *nbytes);
 int ppg_cursor_selected_index(const ppg_cursor *c, int64_t *sel_off, int64_t *recno, int64_t cap);
+
+/* The quality-controlled enumerator: the filtered enumerator whose selection is "hit and pass": every
+ * batch is queried for the pattern, the hits that fail the filter ("read filters" above) are cleared
+ * from the mask on the device, and what remains is selected.  A NULL filter is exactly
+ * ppg_cursor_open_select; a NULL pattern or length 0 makes every record a hit, so the filter alone
+ * selects.  The filter is copied at the call and its AND_MASK bit is ignored; a bad one is
+ * PPG_ARG_ERROR.  ppg_cursor_selected and ppg_cursor_selected_index apply unchanged.
+ *  ppg_cursor_filter_result  the current batch's ppg_read_filter_result, over all its records, hits or
+ *                            not, copied to `result`; PPG_ARG_ERROR on other cursors and before the
+ *                            first ppg_cursor_next. */
+int ppg_cursor_open_filter(ppg_ctx *ctx, const ppg_index *ix, const char *gz_path, int32_t first, int32_t n,
+                           int64_t batch_bytes, int threads, const uint8_t *pattern, int32_t pattern_len,
+                           const void *filter, ppg_cursor **out);
+int ppg_cursor_filter_result(const ppg_cursor *c, void *result);
 
 /* ======================= multi-GPU DecompressAll (one process per GPU) =======================
  * BatchedFASTQ's fan-out (BatchedFASTQ.cs:62-77: a task per chunk) becomes a fan-out over GPUs:

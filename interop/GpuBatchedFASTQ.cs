@@ -154,6 +154,37 @@ public sealed class GpuBatchedFASTQ : IEnumerable<FastqRecord>, IDisposable
         }
     }
 
+    /// <summary>Where(pattern) narrowed to the records that also pass the quality-control filter (length,
+    /// N content, mean quality, low-quality fraction), decided on the GPU as well: only the records that
+    /// hit and pass are brought to the host.  "" as the pattern filters every record.</summary>
+    public IEnumerable<FastqRecord> Where(string pattern, PpgReadFilter filter)
+    {
+        var (first, n) = ChunkRange();
+        nint cur = OpenFilter(first, n, System.Text.Encoding.ASCII.GetBytes(pattern), filter);
+        try
+        {
+            while (true)
+            {
+                var recs = NextSelected(cur);
+                if (recs == null) yield break;
+                foreach (var r in recs) yield return r;
+            }
+        }
+        finally
+        {
+            PpGpu.ppg_cursor_close(cur);
+        }
+    }
+
+    private unsafe nint OpenFilter(int first, int n, byte[] pat, PpgReadFilter filter)
+    {
+        nint cur;
+        fixed (byte* p = pat)
+            PpGpu.Check(PpGpu.ppg_cursor_open_filter(_Ctx, _Ix, _Path, first, n, BatchBytes, _Threads, p, pat.Length,
+                                                     &filter, out cur));
+        return cur;
+    }
+
     private unsafe nint OpenSelect(int first, int n, byte[] pat)
     {
         nint cur;

@@ -64,6 +64,32 @@ public unsafe struct PpgSeqQueryResult // ppg_seq_query_result
     public fixed long Count[5];         // A, C, G, T, other
 }
 
+[StructLayout(LayoutKind.Sequential)]
+public struct PpgReadFilter            // ppg_read_filter
+{
+    public const long Length = 1, Other = 2, Mean = 4, Low = 8, AndMask = 0x100;
+    public long Criteria;               // the bits above
+    public long MinLen;
+    public long MaxLen;                 // -1: no upper bound
+    public long MaxOther;               // Sequence bytes that are not A C G T
+    public long QualBase;               // the Quality byte of quality 0 (33)
+    public long MinMeanMilli;           // 1000 x the least mean quality
+    public long LowQ;                   // a base is low when its quality is below this
+    public long MaxLowMilli;            // 1000 x the largest fraction of low bases
+}
+
+[StructLayout(LayoutKind.Sequential)]
+public unsafe struct PpgReadFilterResult // ppg_read_filter_result
+{
+    public long Records;
+    public long Passed;
+    public fixed long Failed[4];        // length, other, mean quality, low quality
+    public long Bases;
+    public long Other;
+    public long QualBytes;
+    public fixed long QualCount[256];   // Quality bytes by value
+}
+
 internal static unsafe class PpGpu
 {
     const string Lib = "ppgpu";   // libppgpu.so from parallelparsing_amd/
@@ -149,6 +175,14 @@ internal static unsafe class PpGpu
     [DllImport(Lib)] public static extern int ppg_shard_set_seqquery(nint shard, byte* pattern, int patternLen,
         uint* devHitMask, long recCap);
     [DllImport(Lib)] public static extern int ppg_shard_seqquery_ready(nint shard, long* chunkHits, void* result);
+    // read filters: length, N content and quality per record and the pass bits they give (filter: a
+    // PpgReadFilter*, result: a PpgReadFilterResult*; mask and metrics are device pointers)
+    [DllImport(Lib)] public static extern int ppg_read_filter_check(void* filter);
+    [DllImport(Lib)] public static extern int ppg_shard_filter_reads(nint shard, void* filter, uint* devPassMask,
+        long recCap, void* devMetrics, long metricsCap, long* chunkPassed, void* result);
+    [DllImport(Lib)] public static extern int ppg_shard_set_readfilter(nint shard, void* filter, uint* devPassMask,
+        long recCap, void* devMetrics, long metricsCap);
+    [DllImport(Lib)] public static extern int ppg_shard_readfilter_ready(nint shard, long* chunkPassed, void* result);
     // record selection: the records a mask selects, compacted on the GPU (device pointers; a null mask
     // with maskCap 0 selects every record)
     [DllImport(Lib)] public static extern int ppg_shard_select_size(nint shard, uint* devMask, long maskCap,
@@ -187,6 +221,10 @@ internal static unsafe class PpGpu
     [DllImport(Lib)] public static extern int ppg_cursor_selected(nint cursor, byte** bytes, uint** desc,
         out long records, out long nbytes);
     [DllImport(Lib)] public static extern int ppg_cursor_selected_index(nint cursor, long* selOff, long* recno, long cap);
+    // ... narrowed to the hits that pass a read filter (a null filter: ppg_cursor_open_select)
+    [DllImport(Lib)] public static extern int ppg_cursor_open_filter(nint ctx, nint ix, string gzPath, int first, int n,
+        long batchBytes, int threads, byte* pattern, int patternLen, void* filter, out nint cursor);
+    [DllImport(Lib)] public static extern int ppg_cursor_filter_result(nint cursor, void* result);
 
     // ---- multi-GPU DecompressAll: partition + count all-gather over RCCL inside the library ----
     [DllImport(Lib)] public static extern int ppg_comm_unique_id(byte* id /* 128 bytes */);

@@ -592,6 +592,106 @@ class SeqQuery:
         return f"SeqQuery(records={self.records}, hits={self.hits}, bases={self.bases}, counts={self.counts})"
 
 
+class ReadFilter:
+    """A quality-control filter over records (include/ppgpu.h "read filters"); a criterion left at None
+    is not applied.  min_length / max_length bound the Sequence length; max_n the Sequence bytes that are
+    not A C G T; min_mean_quality the mean of the Quality bytes above quality_base; low_quality and
+    max_low_fraction go together: at most that fraction of the Quality bytes may lie below low_quality.
+    The two real-valued thresholds are held as round(1000 * x), the comparisons are exact integers."""
+
+    def __init__(self, min_length=0, max_length=None, max_n=None, min_mean_quality=None, low_quality=None,
+                 max_low_fraction=None, quality_base=33):
+        if (low_quality is None) != (max_low_fraction is None):
+            raise ValueError("ReadFilter: low_quality and max_low_fraction go together")
+        self.min_length, self.max_length, self.max_n = min_length, max_length, max_n
+        self.min_mean_quality, self.low_quality, self.max_low_fraction = min_mean_quality, low_quality, max_low_fraction
+        self.quality_base = quality_base
+
+    def struct(self, and_mask=False):
+        """The ppg_read_filter of this filter (and_mask: with the AND_MASK bit); ValueError when
+        ppg_read_filter_check refuses it."""
+        crit = 0
+        if self.min_length or self.max_length is not None:
+            crit |= _lib.PPG_FILTER_LENGTH
+        if self.max_n is not None:
+            crit |= _lib.PPG_FILTER_OTHER
+        if self.min_mean_quality is not None:
+            crit |= _lib.PPG_FILTER_MEAN
+        if self.low_quality is not None:
+            crit |= _lib.PPG_FILTER_LOW
+        if and_mask:
+            crit |= _lib.PPG_FILTER_AND_MASK
+        f = _lib.PpgReadFilter(
+            crit, int(self.min_length), -1 if self.max_length is None else int(self.max_length),
+            0 if self.max_n is None else int(self.max_n), int(self.quality_base),
+            0 if self.min_mean_quality is None else int(round(1000 * self.min_mean_quality)),
+            0 if self.low_quality is None else int(self.low_quality),
+            0 if self.max_low_fraction is None else int(round(1000 * self.max_low_fraction)))
+        if lib.ppg_read_filter_check(C.byref(f)) != 0:
+            raise ValueError(f"ReadFilter: not a valid filter: {self!r}")
+        return f
+
+    def __repr__(self):
+        return (f"ReadFilter(min_length={self.min_length}, max_length={self.max_length}, max_n={self.max_n}, "
+                f"min_mean_quality={self.min_mean_quality}, low_quality={self.low_quality}, "
+                f"max_low_fraction={self.max_low_fraction}, quality_base={self.quality_base})")
+
+
+def _filter_struct(flt, and_mask=False):
+    """The ppg_read_filter of a ReadFilter, or a _lib.PpgReadFilter as it is (its AND_MASK bit set on demand)."""
+    if isinstance(flt, ReadFilter):
+        return flt.struct(and_mask)
+    if not isinstance(flt, _lib.PpgReadFilter):
+        raise ValueError("expected a ReadFilter")
+    f = _lib.PpgReadFilter.from_buffer_copy(flt)
+    if and_mask:
+        f.criteria |= _lib.PPG_FILTER_AND_MASK
+    return f
+
+
+class ReadFilterResult:
+    """The result of a read filter (include/ppgpu.h "read filters"): `records` measured, `passed`,
+    `failed` (records failing each criterion on its own, by 'length', 'n', 'mean_quality',
+    'low_quality'), `bases`, `other` (Sequence bytes that are not A C G T), `qual_bytes`, `qual_count`
+    (numpy int64[256]: the Quality bytes by value), `chunk_passed` (numpy int64, passes per chunk) and,
+    when asked for, `pass_mask` (a uint32 CUDA tensor in the hit-mask format) and `metrics` (a uint8
+    CUDA tensor of 24-byte rows, see metrics_host)."""
+
+    CRITERIA = ("length", "n", "mean_quality", "low_quality")
+    METRICS_DTYPE = np.dtype([("length", "<u4"), ("other", "<u4"), ("qual_length", "<u4"), ("low", "<u4"),
+                              ("qual_sum", "<u8")])
+
+    def __init__(self, result, chunk_passed=None, pass_mask=None, metrics=None):
+        self.records, self.passed = int(result.records), int(result.passed)
+        self.failed = {c: int(v) for c, v in zip(self.CRITERIA, result.failed)}
+        self.bases, self.other, self.qual_bytes = int(result.bases), int(result.other), int(result.qual_bytes)
+        self.qual_count = np.array(result.qual_count, np.int64)
+        self.chunk_passed = chunk_passed
+        self.pass_mask = pass_mask
+        self.metrics = metrics
+
+    def pass_records(self):
+        """The shard record numbers of the set mask bits, ascending: an int64 tensor on the mask's device."""
+        if self.pass_mask is None:
+            raise ValueError("ReadFilterResult.pass_records: the filter was run without a mask")
+        import torch
+        w = self.pass_mask.view(torch.int32)[:(self.records + 31) // 32]
+        bit = torch.arange(32, dtype=torch.int32, device=w.device)
+        return ((w[:, None] >> bit) & 1).reshape(-1).nonzero().reshape(-1)
+
+    def metrics_host(self):
+        """The metrics rows of the records as a numpy structured array (length, other, qual_length, low, qual_sum)."""
+        if self.metrics is None:
+            raise ValueError("ReadFilterResult.metrics_host: the filter was run without metrics")
+        import torch
+        raw = self.metrics.view(torch.uint8).reshape(-1)[:24 * self.records].cpu().numpy()
+        return raw.view(self.METRICS_DTYPE)
+
+    def __repr__(self):
+        return (f"ReadFilterResult(records={self.records}, passed={self.passed}, failed={self.failed}, "
+                f"bases={self.bases}, other={self.other}, qual_bytes={self.qual_bytes})")
+
+
 class SelectedRecords:
     """The records a mask selects (include/ppgpu.h "record selection"): `bytes` (uint8, the selected
     records' text back to back), `sel_off` (int64, records + 1 offsets into it), `desc` (records x 4:
@@ -739,7 +839,7 @@ class Shard:
 
     def run(self):
         hooked = getattr(self, "_seqpack", None) is not None or getattr(self, "_sq_mask", None) is not None or \
-            getattr(self, "_select", None) is not None
+            getattr(self, "_select", None) is not None or getattr(self, "_rf", None) is not None
         if self._on_device or hooked:
             self._torch_order()   # the caller may have rewritten comp (or the hooks' tensors) since the last run
         check(lib.ppg_shard_run(self._h), "DecompressAll")
@@ -891,6 +991,69 @@ class Shard:
         if lib.ppg_shard_seqquery_ready(self._h, _ptr(ch), C.byref(res)) != 1:
             return None
         return SeqQuery(res, ch, getattr(self, "_sq_mask", None))
+
+    def filter_reads(self, flt, mask=False, metrics=False):
+        """The read filter `flt` (a ReadFilter) over the records of a one-batch shard after its run
+        (ppg_shard_filter_reads), as a ReadFilterResult.  mask=True also returns the per-record pass bits
+        as a uint32 CUDA tensor on this device; a tensor of hit-mask words instead (a query's hit_mask)
+        is ANDed in place with them.  metrics=True also returns the per-record metrics rows.  Ordered
+        after torch's stream, complete on return."""
+        import torch
+        dev = torch.device("cuda", self.dev.device)
+        nrec = max(self.total_records, 0)
+        pm, cap, and_mask = None, 0, False
+        if mask is True:
+            cap = (nrec + 31) // 32 * 32
+            pm = torch.zeros(cap // 32, dtype=torch.int32, device=dev).view(torch.uint32)
+        elif mask is not False and mask is not None:
+            _, cap, pm = _mask_arg(mask, "filter_reads")
+            and_mask = True
+        mt = torch.zeros((nrec, 24), dtype=torch.uint8, device=dev) if metrics else None
+        f = _filter_struct(flt, and_mask)
+        self._torch_order()
+        res, ch = _lib.PpgReadFilterResult(), np.zeros(self.n, np.int64)
+        check(lib.ppg_shard_filter_reads(self._h, C.byref(f), C.c_void_p(pm.data_ptr()) if cap else None, cap,
+                                         C.c_void_p(mt.data_ptr()) if metrics and nrec else None, nrec if metrics else 0,
+                                         _ptr(ch), C.byref(res)), "filter_reads")
+        return ReadFilterResult(res, ch, pm, mt)
+
+    def set_readfilter(self, flt, mask=None, metrics=None, and_mask=False):
+        """From the next run on, every output batch is measured and filtered by `flt` while its output is
+        resident (ppg_shard_set_readfilter): works for shards of any number of batches, and runs after a
+        set_seqquery hook and before a set_select hook; the result is `readfilter` after the run.
+        mask: an int32 / uint32 CUDA tensor of at least ceil(records / 32) words for the pass bits
+        (and_mask=True: its bits are ANDed with them instead, e.g. the query hook's mask); metrics: a
+        uint8 CUDA tensor of at least 24 * records bytes for the metrics rows.  flt=None turns it off."""
+        if flt is None:
+            check(lib.ppg_shard_set_readfilter(self._h, None, None, 0, None, 0), "set_readfilter")
+            self._rf = None
+            return self
+        import torch
+        ptr, cap = None, 0
+        if mask is not None:
+            ptr, cap, mask = _mask_arg(mask, "set_readfilter")
+            if mask is not None:
+                mask = mask.view(torch.uint32)
+        mptr, mcap = None, 0
+        if metrics is not None:
+            if not (metrics.is_cuda and metrics.dtype == torch.uint8 and metrics.is_contiguous()):
+                raise ValueError("set_readfilter: metrics must be a contiguous uint8 CUDA tensor")
+            mcap = metrics.numel() // 24
+            mptr = C.c_void_p(metrics.data_ptr()) if mcap else None
+        f = _filter_struct(flt, and_mask)
+        self._rf = (mask, metrics)   # kept alive while the library may write them
+        self._torch_order()
+        check(lib.ppg_shard_set_readfilter(self._h, C.byref(f), ptr, cap, mptr, mcap), "set_readfilter")
+        return self
+
+    @property
+    def readfilter(self):
+        """The ReadFilterResult of the last run's set_readfilter hook, or None when that run did not complete one."""
+        res, ch = _lib.PpgReadFilterResult(), np.zeros(self.n, np.int64)
+        if lib.ppg_shard_readfilter_ready(self._h, _ptr(ch), C.byref(res)) != 1:
+            return None
+        rf = getattr(self, "_rf", None) or (None, None)
+        return ReadFilterResult(res, ch, rf[0], rf[1])
 
     def select_size(self, mask=None):
         """(records, bytes) a selection by `mask` holds, after a run of any number of batches
@@ -1122,20 +1285,33 @@ class Cursor:
 
     pattern=b"..." opens the filtered enumerator (ppg_cursor_open_select; not with packed=True): every
     batch is searched for the pattern on the GPU and carries only Batch.selected, a host SelectedRecords
-    of the records whose Sequence contains it (b"": every record); nrecords counts the records scanned."""
+    of the records whose Sequence contains it (b"": every record); nrecords counts the records scanned.
+
+    filter=ReadFilter(...) (ppg_cursor_open_filter; alone or with pattern=, not with packed=True) narrows
+    that selection to the hits that pass the filter, decided on the GPU as well; Batch.filter_result is
+    then the batch's ReadFilterResult, over all its records."""
 
     def __init__(self, index, gzip_path, first=0, n=None, batch_bytes=1 << 30, threads=8, device=None,
-                 packed=False, quality=True, pattern=None):
-        if packed and pattern is not None:
-            raise ValueError("Cursor: packed=True and pattern= exclude each other")
+                 packed=False, quality=True, pattern=None, filter=None):   # noqa: A002
+        if packed and (pattern is not None or filter is not None):
+            raise ValueError("Cursor: packed=True and pattern= / filter= exclude each other")
+        if filter is not None and pattern is None:
+            pattern = b""
         self.index = index
         self.dev = device or Device.default()
         if n is None:
             n = index.Count - 1 - first
         self.packed, self.quality = bool(packed), bool(quality)
         self.select = pattern is not None
+        self.filtered = filter is not None
         h = C.c_void_p()
-        if self.select:
+        if self.filtered:
+            pat, m = _pattern_arg(pattern)
+            f = _filter_struct(filter)
+            check(lib.ppg_cursor_open_filter(self.dev.handle, index.handle, os.fsencode(gzip_path), int(first), int(n),
+                                             int(batch_bytes), int(threads), pat, m, C.byref(f), C.byref(h)),
+                  "ppg_cursor_open_filter")
+        elif self.select:
             pat, m = _pattern_arg(pattern)
             check(lib.ppg_cursor_open_select(self.dev.handle, index.handle, os.fsencode(gzip_path), int(first), int(n),
                                              int(batch_bytes), int(threads), pat, m, C.byref(h)), "ppg_cursor_open_select")
@@ -1170,7 +1346,13 @@ class Cursor:
             return None
         check(rc, "ppg_cursor_next")
         return Batch(b, self.packed_reads(b.nrecords) if self.packed else None,
-                     self.selected_records() if self.select else None)
+                     self.selected_records() if self.select else None, self.filter_result() if self.filtered else None)
+
+    def filter_result(self):
+        """The current batch's ReadFilterResult (ppg_cursor_filter_result): totals alone."""
+        res = _lib.PpgReadFilterResult()
+        check(lib.ppg_cursor_filter_result(self._h, C.byref(res)), "ppg_cursor_filter_result")
+        return ReadFilterResult(res)
 
     def selected_records(self):
         """The current batch's selection (ppg_cursor_selected / ppg_cursor_selected_index) as a host
@@ -1221,15 +1403,17 @@ class Cursor:
 class Batch:
     """One ppg_batch: text (uint8), raw_off / rec_off (int64, nchunks + 1), desc (nrecords x 4).  A
     packed cursor's batch has text = desc = None and `packed`, a host PackedReads; a select cursor's
-    has text = desc = None and `selected`, a host SelectedRecords."""
+    has text = desc = None and `selected`, a host SelectedRecords, and with a filter `filter_result`, the
+    batch's ReadFilterResult."""
 
-    def __init__(self, b, packed=None, selected=None):
+    def __init__(self, b, packed=None, selected=None, filter_result=None):
         self.first_chunk, self.nchunks = b.first_chunk, b.nchunks
         self.record_base, self.nrecords = b.record_base, b.nrecords
         self.raw_off = np.ctypeslib.as_array(b.raw_off, (b.nchunks + 1,))
         self.rec_off = np.ctypeslib.as_array(b.rec_off, (b.nchunks + 1,))
         self.packed = packed
         self.selected = selected
+        self.filter_result = filter_result
         if packed is not None or selected is not None or not b.text:
             self.text = self.desc = None
             return
@@ -1328,16 +1512,17 @@ class BatchedFASTQ:
         finally:
             cur.close()
 
-    def Where(self, pattern):
+    def Where(self, pattern=None, filter=None):   # noqa: A002
         """The records whose Sequence contains `pattern` (the body of Benchmark/Naive.cs RunPattern's
         loop: foreach record, if record.Sequence.Contains(pattern)), in canonical order, through the
         select cursor (ppg_cursor_open_select) over chunk_range(): searched and compacted on the GPU,
         only the hits reach the host.  Each batch's bytes are copied out before the next one is
-        requested.  pattern as in CountPattern (None or b"": every record)."""
+        requested.  pattern as in CountPattern (None or b"": every record).  filter: a ReadFilter the
+        records must pass as well (ppg_cursor_open_filter), decided on the GPU too."""
         first, n = self.chunk_range()
         cur = Cursor(self.index, self.gzip_path, first=first, n=n, batch_bytes=self.batch_bytes,
                      threads=16 if self.enable_ssd_optimization else 8, device=self.dev,
-                     pattern=b"" if pattern is None else pattern)
+                     pattern=b"" if pattern is None else pattern, filter=filter)
         try:
             for b in cur:
                 sel = b.selected
@@ -1352,9 +1537,9 @@ class BatchedFASTQ:
     # batches of whole chunks no larger than this, so a file of any size is scanned in bounded memory
     query_out_capacity = 256 << 20
 
-    def _query(self, pattern):
+    def _query_shard(self):
         if self.world is not None:
-            raise ValueError("CountPattern / CountBases run in a single process (no rank / world)")
+            raise ValueError("CountPattern / CountBases / CountPassing run in a single process (no rank / world)")
         cap, sh = getattr(self, "_qshard", None) or (None, None)
         if sh is None or cap != self.query_out_capacity:
             # the file's compressed bytes go to the device once (from the page cache, no host copy) and
@@ -1366,7 +1551,20 @@ class BatchedFASTQ:
             cap = self.query_out_capacity
             sh = Shard(self.index, comp, 0, n, device=self.dev, out_capacity=cap)
             self._qshard = (cap, sh)
-        return sh.set_seqquery(pattern).run().seqquery
+        return sh
+
+    def _query(self, pattern):
+        return self._query_shard().set_readfilter(None).set_seqquery(pattern).run().seqquery
+
+    def CountPassing(self, filter):   # noqa: A002
+        """The ReadFilterResult of `filter` (a ReadFilter) over the file: how many records pass, how many
+        fail each criterion, and the totals, measured on the GPU batch by batch (Shard.set_readfilter):
+        no record text reaches the host."""
+        return self._query_shard().set_seqquery(None).set_readfilter(filter).run().readfilter
+
+    def QualityCounts(self):
+        """numpy int64[256]: the bytes of every Quality line by value, counted on the GPU batch by batch."""
+        return self.CountPassing(ReadFilter()).qual_count
 
     def CountPattern(self, pattern):
         """Number of records whose Sequence contains `pattern` (Benchmark/Naive.cs RunPattern:

@@ -124,6 +124,12 @@ _SIGS = {
     "ppg_shard_query_seq": (C.c_int, [vp, vp, i32, vp, i64, vp, vp]),
     "ppg_shard_set_seqquery": (C.c_int, [vp, vp, i32, vp, i64]),
     "ppg_shard_seqquery_ready": (C.c_int, [vp, vp, vp]),
+    "ppg_read_filter_check": (C.c_int, [vp]),
+    "ppg_shard_filter_reads": (C.c_int, [vp, vp, vp, i64, vp, i64, vp, vp]),
+    "ppg_shard_set_readfilter": (C.c_int, [vp, vp, vp, i64, vp, i64]),
+    "ppg_shard_readfilter_ready": (C.c_int, [vp, vp, vp]),
+    "ppg_cursor_open_filter": (C.c_int, [vp, vp, C.c_char_p, i32, i32, i64, C.c_int, vp, i32, vp, P(vp)]),
+    "ppg_cursor_filter_result": (C.c_int, [vp, vp]),
     "ppg_shard_select_size": (C.c_int, [vp, vp, i64, P(i64), P(i64)]),
     "ppg_shard_select_records": (C.c_int, [vp, vp, i64, vp, vp, vp, i64, vp, i64, P(i64), P(i64)]),
     "ppg_shard_set_select": (C.c_int, [vp, vp, i64, vp, vp, vp, i64, vp, i64]),
@@ -175,6 +181,22 @@ class PpgPairResult(C.Structure):
 class PpgSeqQueryResult(C.Structure):
     """ppg_seq_query_result (include/ppgpu.h)."""
     _fields_ = [("records", C.c_int64), ("hits", C.c_int64), ("bases", C.c_int64), ("count", C.c_int64 * 5)]
+
+
+class PpgReadFilter(C.Structure):
+    """ppg_read_filter (include/ppgpu.h)."""
+    _fields_ = [("criteria", C.c_int64), ("min_len", C.c_int64), ("max_len", C.c_int64), ("max_other", C.c_int64),
+                ("qual_base", C.c_int64), ("min_mean_milli", C.c_int64), ("low_q", C.c_int64),
+                ("max_low_milli", C.c_int64)]
+
+
+class PpgReadFilterResult(C.Structure):
+    """ppg_read_filter_result (include/ppgpu.h)."""
+    _fields_ = [("records", C.c_int64), ("passed", C.c_int64), ("failed", C.c_int64 * 4), ("bases", C.c_int64),
+                ("other", C.c_int64), ("qual_bytes", C.c_int64), ("qual_count", C.c_int64 * 256)]
+
+
+PPG_FILTER_LENGTH, PPG_FILTER_OTHER, PPG_FILTER_MEAN, PPG_FILTER_LOW, PPG_FILTER_AND_MASK = 1, 2, 4, 8, 0x100
 
 
 for _name, (_res, _args) in _SIGS.items():

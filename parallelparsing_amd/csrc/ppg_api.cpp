@@ -40,6 +40,10 @@ static bool seqquery_linked() {
     return seq_linked() && ppg_launch_seq_query && ppg_launch_seq_query_chunks && ppg_launch_seq_query_totals;
 }
 
+static bool readfilter_linked() {
+    return seq_linked() && ppg_launch_rf_measure && ppg_launch_rf_decide && ppg_launch_rf_totals;
+}
+
 static bool select_linked() {
     return ppg_launch_sel_count && ppg_launch_sel_scan && ppg_launch_sel_place && ppg_launch_sel_copy;
 }
@@ -697,6 +701,7 @@ int shard_seq_query(ppg_shard *sh, int32_t b0, int32_t b1, const uint32_t *recs,
     if (!seqquery_linked()) return PPG_UNSUPPORTED;
     int64_t total = 0;
     if (int rc = shard_seq_layout(sh, b0, b1, recs, &total)) return rc;
+    sh->sq_total = total;
     HIPCHK(grow_buf(sh->sq_off, (size_t)tot + 1));
     HIPCHK(grow_buf(sh->sq_len, (size_t)tot + 1));
     HIPCHK(sh->sq_acc.alloc(8));
@@ -753,6 +758,75 @@ bool seqquery_pattern(const uint8_t *pattern, int32_t m, PpgSeqPattern *pat) {
 
 static bool seqquery_mask_ok(const uint32_t *mask, int64_t rec_cap) {
     return rec_cap >= 0 && rec_cap % 32 == 0 && ((uintptr_t)mask & 3) == 0 && (mask != nullptr || rec_cap == 0);
+}
+
+// ---- read filters (ppg_readfilter.hip) ----
+// the rules of include/ppgpu.h "read filters"; host only
+static bool readfilter_ok(const void *filter, PpgReadFilter *out) {
+    if (!filter) return false;
+    PpgReadFilter f;
+    memcpy(&f, filter, sizeof f);
+    if (f.criteria & ~(int64_t)0x10F) return false;
+    if (f.min_len < 0 || f.max_len < -1 || (f.max_len >= 0 && f.max_len < f.min_len)) return false;
+    if ((f.criteria & 2) && f.max_other < 0) return false;
+    if (f.qual_base < 0 || f.qual_base > 255) return false;
+    if (f.low_q < 0 || f.low_q > 256 || f.qual_base + f.low_q > 256) return false;
+    if (f.max_low_milli < 0 || f.max_low_milli > 1000) return false;
+    if (f.min_mean_milli > 255000 || f.min_mean_milli < -255000) return false;
+    if (out) *out = f;
+    return true;
+}
+
+static bool readfilter_bufs_ok(const PpgReadFilter &f, const uint32_t *mask, int64_t rec_cap, const uint8_t *metrics,
+                               int64_t metrics_cap) {
+    if (!seqquery_mask_ok(mask, rec_cap) || ((f.criteria & 0x100) && !mask)) return false;
+    return metrics_cap >= 0 && ((uintptr_t)metrics & 7) == 0 && (metrics != nullptr || metrics_cap == 0);
+}
+
+int shard_read_filter(ppg_shard *sh, int32_t b0, int32_t b1, const uint32_t *recs, int64_t rec0, int64_t tot,
+                      const PpgReadFilter &flt, uint32_t *mask, uint8_t *metrics, bool first, bool laid_out) {
+    hipStream_t s = shard_stream(sh);
+    const int nb = b1 - b0;
+    if (!readfilter_linked()) return PPG_UNSUPPORTED;
+    int64_t total = sh->sq_total;
+    if (!laid_out) {
+        if (int rc = shard_seq_layout(sh, b0, b1, recs, &total)) return rc;
+        HIPCHK(grow_buf(sh->sq_off, (size_t)tot + 1));
+        HIPCHK(grow_buf(sh->sq_len, (size_t)tot + 1));
+        HIPCHK(ppg_launch_seq_offsets(s, sh->res.p + b0, sh->info.p + b0, sh->base.p + b0, recs, sh->sp_cbase.p, 0,
+                                      sh->sq_off.p, sh->sq_len.p, nb));
+    }
+    HIPCHK(grow_buf(sh->rf_rsc, 2 * ((size_t)tot + 1)));
+    HIPCHK(sh->rf_acc.alloc(kRfAcc));
+    HIPCHK(sh->rf_host.alloc(8 * ((size_t)kRfAcc + (size_t)sh->n)));
+    if (first) HIPCHK(hipMemsetAsync(sh->rf_acc.p, 0, 8 * (size_t)kRfAcc, s));
+    if (tot) HIPCHK(hipMemsetAsync(sh->rf_rsc.p, 0, 16 * (size_t)tot, s));
+    if (mask && !(flt.criteria & 0x100)) {
+        // as the query: the words whose first bit is this batch's or later; the word a batch shares with
+        // the one before it was cleared by that batch.  (AND_MASK changes this batch's bits alone.)
+        const uint64_t w0 = ((uint64_t)rec0 + 31) / 32, w1 = ((uint64_t)rec0 + (uint64_t)tot + 31) / 32;
+        if (w1 > w0) HIPCHK(hipMemsetAsync(mask + w0, 0, 4 * (size_t)(w1 - w0), s));
+    }
+    HIPCHK(ppg_launch_rf_measure(s, sh->out.p, sh->jobs.p + b0, sh->offs.p, sh->oref.p + b0, sh->info.p + b0,
+                                 sh->base.p + b0, recs, sh->sp_cbase.p, sh->sq_off.p, sh->sq_len.p, (uint64_t)total,
+                                 (uint32_t)(flt.qual_base + flt.low_q), sh->rf_rsc.p, sh->rf_acc.p, nb, sh->rf_hist));
+    int64_t *host = (int64_t *)sh->rf_host.p;
+    HIPCHK(ppg_launch_rf_decide(s, sh->out.p, sh->jobs.p + b0, sh->res.p + b0, sh->offs.p, sh->oref.p + b0, sh->info.p + b0,
+                                sh->base.p + b0, recs, sh->rf_rsc.p, &flt, mask, (uint64_t)rec0, metrics, sh->rf_acc.p,
+                                host + kRfAcc + b0, nb));
+    HIPCHK(ppg_launch_rf_totals(s, sh->rf_acc.p, host));
+    return PPG_OK;
+}
+
+// what the last completed filter left in pinned memory
+void readfilter_outputs(const ppg_shard *sh, int64_t *chunk_passed, void *result) {
+    const int64_t *host = (const int64_t *)sh->rf_host.p;
+    if (!host) {   // a shard without chunks: no batch ran
+        if (result) memset(result, 0, sizeof(ppg_read_filter_result));
+        return;
+    }
+    if (result) memcpy(result, host, sizeof(ppg_read_filter_result));
+    if (chunk_passed && sh->n) memcpy(chunk_passed, host + kRfAcc, 8 * (size_t)sh->n);
 }
 
 // ---- record selection (ppg_seqselect.hip) ----
@@ -904,8 +978,17 @@ int batch_collect(ppg_shard *sh, int32_t b0, int32_t b1, float &total_ms) {
                                      sh->sq_mask, b0 == 0))
             return rc;
     }
-    // selection of the batch's records, likewise and last: a query hook has filled this batch's bits
-    // of a mask the two share (ppg_shard_set_select)
+    // read filter of the batch, likewise, after the query: with AND_MASK on the query's mask it sees
+    // this batch's hit bits (ppg_shard_set_readfilter)
+    if (sh->rf_on) {
+        const int64_t after = sh->total_records + (int64_t)tot;
+        if ((sh->rf_mask && after > sh->rf_rec_cap) || (sh->rf_metrics && after > sh->rf_metrics_cap)) return PPG_BUF_ERROR;
+        if (int rc = shard_read_filter(sh, b0, b1, sh->recs.p + r0, sh->total_records, (int64_t)tot, sh->rf_flt, sh->rf_mask,
+                                       sh->rf_metrics, b0 == 0, sh->sq_on != 0))
+            return rc;
+    }
+    // selection of the batch's records, likewise and last: a query or filter hook has filled this
+    // batch's bits of a mask they share (ppg_shard_set_select)
     if (sh->sel_on)
         if (int rc = select_hook(sh, b0, b1, (int64_t)tot)) return rc;
     sh->t_inflate += a;
@@ -957,11 +1040,13 @@ int ppg_shard_run(ppg_shard *sh) {
     sh->keys_written = 0;
     sh->sp_written = 0;
     sh->sq_written = 0;
+    sh->rf_written = 0;
     sh->sel_written = 0;
     sh->last_rc = shard_run(sh);
     sh->keys_written = sh->last_rc == PPG_OK && sh->keys_dev != nullptr;
     sh->sp_written = sh->last_rc == PPG_OK && sh->sp_off != nullptr;
     sh->sq_written = sh->last_rc == PPG_OK && sh->sq_on;
+    sh->rf_written = sh->last_rc == PPG_OK && sh->rf_on;
     sh->sel_written = sh->last_rc == PPG_OK && sh->sel_on;
     return sh->last_rc;
 }
@@ -1287,6 +1372,52 @@ int ppg_shard_seqquery_ready(ppg_shard *sh, int64_t *chunk_hits, void *result) {
     return 1;
 }
 
+// ---- read filters: the sequence queries entry points' counterparts ----
+int ppg_read_filter_check(const void *filter) { return readfilter_ok(filter, nullptr) ? PPG_OK : PPG_ARG_ERROR; }
+
+int ppg_shard_filter_reads(ppg_shard *sh, const void *filter, uint32_t *dev_pass_mask, int64_t rec_cap, void *dev_metrics,
+                           int64_t metrics_cap, int64_t *chunk_passed, void *result) {
+    PpgReadFilter flt;
+    if (!sh || !sh->ran || sh->batches.size() != 1 || !readfilter_ok(filter, &flt) ||
+        !readfilter_bufs_ok(flt, dev_pass_mask, rec_cap, (const uint8_t *)dev_metrics, metrics_cap))
+        return PPG_ARG_ERROR;
+    if (!readfilter_linked()) return PPG_UNSUPPORTED;
+    if ((dev_pass_mask && sh->total_records > rec_cap) || (dev_metrics && sh->total_records > metrics_cap))
+        return PPG_BUF_ERROR;
+    HIPCHK(hipSetDevice(sh->ctx->device));
+    sh->rf_written = 0;   // the pinned outputs are rewritten: an earlier run's hook result is gone
+    if (int rc = shard_read_filter(sh, 0, sh->n, sh->recs.p, 0, sh->total_records, flt, dev_pass_mask,
+                                   (uint8_t *)dev_metrics, true, false))
+        return rc;
+    HIPCHK(hipStreamSynchronize(shard_stream(sh)));
+    readfilter_outputs(sh, chunk_passed, result);
+    return PPG_OK;
+}
+
+int ppg_shard_set_readfilter(ppg_shard *sh, const void *filter, uint32_t *dev_pass_mask, int64_t rec_cap, void *dev_metrics,
+                             int64_t metrics_cap) {
+    if (!sh) return PPG_ARG_ERROR;
+    PpgReadFilter flt = {};
+    if (filter && (!readfilter_ok(filter, &flt) ||
+                   !readfilter_bufs_ok(flt, dev_pass_mask, rec_cap, (const uint8_t *)dev_metrics, metrics_cap)))
+        return PPG_ARG_ERROR;
+    sh->rf_on = filter ? 1 : 0;
+    sh->rf_flt = flt;
+    sh->rf_mask = filter ? dev_pass_mask : nullptr;
+    sh->rf_rec_cap = filter ? rec_cap : 0;
+    sh->rf_metrics = filter ? (uint8_t *)dev_metrics : nullptr;
+    sh->rf_metrics_cap = filter ? metrics_cap : 0;
+    sh->rf_written = 0;   // completed by the next run, not by an earlier one
+    return PPG_OK;
+}
+
+int ppg_shard_readfilter_ready(ppg_shard *sh, int64_t *chunk_passed, void *result) {
+    if (!sh) return PPG_ARG_ERROR;
+    if (!sh->rf_written) return 0;
+    readfilter_outputs(sh, chunk_passed, result);
+    return 1;
+}
+
 // ---- record selection: the sequence queries entry points' counterparts ----
 static bool select_bufs_ok(const int64_t *recno, const int64_t *sel_off, const uint32_t *desc, int64_t sel_cap,
                            const uint8_t *bytes, int64_t byte_cap) {
@@ -1562,6 +1693,79 @@ int ppgx_seqquery_times(ppg_shard *sh, const uint8_t *pattern, int32_t m, int re
     (void)hipEventDestroy(e0);
     (void)hipEventDestroy(e1);
     sh->sq_written = 0;   // the pinned outputs no longer belong to a run
+    return rc;
+}
+
+// Measurement hook of tools/readfilter_probe.py (not part of the ABI), as ppgx_seqquery_times: on a
+// one-batch shard after its run, the median of reps launches after one warm-up each, into ms[0..2]: the
+// layout (totals + scan + seq_off / seq_len), the measure kernel with the zeroing of its scratch, and the
+// decide kernel (with the clearing of its mask words) + the totals' store.  with_mask / with_metrics:
+// the decide kernel writes shard scratch planes of that size.  hist: ppg_rf_measure's histogram variant
+// (kRfHistRuns / kRfHistBytes).  The accumulators keep adding over the launches: only the times are meaningful.
+int ppgx_readfilter_times(ppg_shard *sh, const void *filter, int with_mask, int with_metrics, int hist, int reps,
+                          float *ms) {
+    PpgReadFilter flt;
+    if (!sh || !sh->ran || sh->batches.size() != 1 || !ms || reps < 1 || !readfilter_ok(filter, &flt) ||
+        (flt.criteria & 0x100) || (hist != kRfHistRuns && hist != kRfHistBytes))
+        return PPG_ARG_ERROR;
+    HIPCHK(hipSetDevice(sh->ctx->device));
+    hipStream_t s = shard_stream(sh);
+    const int64_t tot = sh->total_records;
+    DevBuf<uint32_t> words;
+    DevBuf<uint8_t> rows;
+    if (with_mask) HIPCHK(words.alloc((size_t)tot / 32 + 1));
+    if (with_metrics) HIPCHK(rows.alloc(24 * (size_t)tot + 8));
+    // one whole filter first: it sizes the scratch buffers and leaves the layout in place
+    const int hist_was = sh->rf_hist;
+    sh->rf_hist = hist;
+    int rc = shard_read_filter(sh, 0, sh->n, sh->recs.p, 0, tot, flt, words.p, rows.p, true, false);
+    sh->rf_hist = hist_was;
+    if (rc != PPG_OK) return rc;
+    HIPCHK(hipStreamSynchronize(s));
+    const uint64_t total = *(volatile uint64_t *)sh->sp_htot.p;
+    int64_t *host = (int64_t *)sh->rf_host.p;
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    HIPCHK(hipEventCreate(&e0));
+    HIPCHK(hipEventCreate(&e1));
+    for (int what = 0; what < 3 && rc == PPG_OK; what++) {
+        std::vector<float> t;
+        for (int r = 0; r <= reps && rc == PPG_OK; r++) {
+            hipError_t e = hipEventRecord(e0, s);
+            if (e == hipSuccess && what == 0) {
+                e = ppg_launch_seq_totals(s, sh->res.p, sh->info.p, sh->base.p, sh->recs.p, sh->sp_ctot.p, sh->n);
+                if (e == hipSuccess) e = ppg_launch_seq_scan(s, sh->sp_ctot.p, sh->sp_cbase.p, (uint64_t *)sh->sp_htot.p, sh->n);
+                if (e == hipSuccess)
+                    e = ppg_launch_seq_offsets(s, sh->res.p, sh->info.p, sh->base.p, sh->recs.p, sh->sp_cbase.p, 0,
+                                               sh->sq_off.p, sh->sq_len.p, sh->n);
+            } else if (e == hipSuccess && what == 1) {
+                if (tot) e = hipMemsetAsync(sh->rf_rsc.p, 0, 16 * (size_t)tot, s);
+                if (e == hipSuccess)
+                    e = ppg_launch_rf_measure(s, sh->out.p, sh->jobs.p, sh->offs.p, sh->oref.p, sh->info.p, sh->base.p,
+                                              sh->recs.p, sh->sp_cbase.p, sh->sq_off.p, sh->sq_len.p, total,
+                                              (uint32_t)(flt.qual_base + flt.low_q), sh->rf_rsc.p, sh->rf_acc.p, sh->n, hist);
+            } else if (e == hipSuccess) {
+                if (words.p) e = hipMemsetAsync(words.p, 0, 4 * (size_t)((tot + 31) / 32), s);
+                if (e == hipSuccess)
+                    e = ppg_launch_rf_decide(s, sh->out.p, sh->jobs.p, sh->res.p, sh->offs.p, sh->oref.p, sh->info.p,
+                                             sh->base.p, sh->recs.p, sh->rf_rsc.p, &flt, words.p, 0, rows.p, sh->rf_acc.p,
+                                             host + kRfAcc, sh->n);
+                if (e == hipSuccess) e = ppg_launch_rf_totals(s, sh->rf_acc.p, host);
+            }
+            if (e == hipSuccess) e = hipEventRecord(e1, s);
+            if (e == hipSuccess) e = hipEventSynchronize(e1);
+            float v = 0;
+            if (e == hipSuccess) e = hipEventElapsedTime(&v, e0, e1);
+            if (e != hipSuccess) rc = PPG_DEVICE_ERROR;
+            if (r) t.push_back(v);   // (r = 0 warms up)
+        }
+        if (rc == PPG_OK) {
+            std::sort(t.begin(), t.end());
+            ms[what] = t[t.size() / 2];
+        }
+    }
+    (void)hipEventDestroy(e0);
+    (void)hipEventDestroy(e1);
+    sh->rf_written = 0;   // the pinned outputs no longer belong to a run
     return rc;
 }
 

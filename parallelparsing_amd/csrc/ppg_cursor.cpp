@@ -112,6 +112,8 @@ struct ppg_cursor {
     bool select = false;                // batches carry the records whose Sequence contains pat
     PpgSeqPattern pat = {};
     int32_t pat_m = 0;
+    bool filter = false;                // ... and pass flt (ppg_cursor_open_filter): the selection is "hit and pass"
+    PpgReadFilter flt = {};
     const Slot *cur = nullptr;          // the batch handed out last (the packed / selected accessors read it)
     int64_t cur_base = 0;               // ... and its record_base
     int64_t pk_rec = 0, pk_bases = 0;   // packed slots: records / padded bases they are sized for at open
@@ -190,7 +192,7 @@ struct ppg_cursor {
         // a select slot: the selection buffers for the whole batch's text on the device, the scratch of the
         // query and the selection (~40 B per record); pinned, what batches select: unknown before the first
         // count pass unless every record is selected (no pattern), which is the whole text
-        const bool select_all = select && pat_m == 0;
+        const bool select_all = select && pat_m == 0 && !filter;
         // (pin_select: the text, and 32 B of descriptor, record number and offset per record)
         const double sel_pinned = select_all ? (double)rmax + 32.0 * (double)pk_rec : (double)(256 << 10) + 32.0 * 1024;
         const double host_slot = (double)cmax + (packed ? pk_bytes : select ? sel_pinned : (double)rmax * 1.125);
@@ -343,6 +345,10 @@ struct ppg_cursor {
             if ((size_t)s.nrec + 1 > s.dsel_off.n)
                 if (int rc = grow_select(s, s.nrec + s.nrec / 4)) return rc;
             if (int rc = shard_seq_query(&s.sh, 0, m, s.sh.recs.p, 0, s.nrec, pat, pat_m, s.dsel_mask.p, true)) return rc;
+            // the filter clears the bits of the hits that fail it, on the layout the query has just made
+            if (filter)
+                if (int rc = shard_read_filter(&s.sh, 0, m, s.sh.recs.p, 0, s.nrec, flt, s.dsel_mask.p, nullptr, true, true))
+                    return rc;
             if (int rc = shard_select_sizes(&s.sh, 0, m, s.sh.recs.p, s.dsel_mask.p, 0, &s.sel_records, &s.sel_nbytes))
                 return rc;
             if ((size_t)s.sel_nbytes + 16 > s.dsel_bytes.n) return PPG_BUF_ERROR;   // a selection is part of the text: never
@@ -431,7 +437,7 @@ extern "C" {
 
 static int cursor_open(ppg_ctx *ctx, const ppg_index *ix, const char *gz_path, int32_t first, int32_t n,
                        int64_t batch_bytes, int threads, bool packed, bool quality, const PpgSeqPattern *pat,
-                       int32_t pat_m, ppg_cursor **out) {
+                       int32_t pat_m, const void *filter, ppg_cursor **out) {
     if (!ctx || !ix || !gz_path || !out || first < 0 || n < 0 || (size_t)first + (size_t)n + 1 > ix->pts.size())
         return PPG_ARG_ERROR;
     if (int v = ppg_index_validate(ix, first, n)) return v;
@@ -449,6 +455,11 @@ static int cursor_open(ppg_ctx *ctx, const ppg_index *ix, const char *gz_path, i
         c->select = true;
         c->pat = *pat;
         c->pat_m = pat_m;
+    }
+    if (filter) {   // (checked by the caller; AND_MASK is what a cursor does in any case)
+        c->filter = true;
+        memcpy(&c->flt, filter, sizeof c->flt);
+        c->flt.criteria |= 0x100;
     }
     if (const char *e = getenv("PPG_CURSOR_SLOTS")) c->nslots = std::min(kMaxSlots, std::max(2, atoi(e)));
     if (const char *e = getenv("PPG_CURSOR_PACK")) c->pack = std::min(2, std::max(0, atoi(e)));
@@ -491,13 +502,13 @@ static int cursor_open(ppg_ctx *ctx, const ppg_index *ix, const char *gz_path, i
 
 int ppg_cursor_open(ppg_ctx *ctx, const ppg_index *ix, const char *gz_path, int32_t first, int32_t n,
                     int64_t batch_bytes, int threads, ppg_cursor **out) {
-    return cursor_open(ctx, ix, gz_path, first, n, batch_bytes, threads, false, false, nullptr, 0, out);
+    return cursor_open(ctx, ix, gz_path, first, n, batch_bytes, threads, false, false, nullptr, 0, nullptr, out);
 }
 
 int ppg_cursor_open_packed(ppg_ctx *ctx, const ppg_index *ix, const char *gz_path, int32_t first, int32_t n,
                            int64_t batch_bytes, int threads, int32_t planes, ppg_cursor **out) {
     if (planes & ~1) return PPG_ARG_ERROR;
-    return cursor_open(ctx, ix, gz_path, first, n, batch_bytes, threads, true, (planes & 1) != 0, nullptr, 0, out);
+    return cursor_open(ctx, ix, gz_path, first, n, batch_bytes, threads, true, (planes & 1) != 0, nullptr, 0, nullptr, out);
 }
 
 int ppg_cursor_packed(const ppg_cursor *c, uint32_t **bases, uint32_t **mask, uint8_t **qual, uint32_t **seq_len,
@@ -525,7 +536,22 @@ int ppg_cursor_open_select(ppg_ctx *ctx, const ppg_index *ix, const char *gz_pat
                            ppg_cursor **out) {
     PpgSeqPattern pat;
     if (!seqquery_pattern(pattern, pattern_len, &pat)) return PPG_ARG_ERROR;
-    return cursor_open(ctx, ix, gz_path, first, n, batch_bytes, threads, false, false, &pat, pattern_len, out);
+    return cursor_open(ctx, ix, gz_path, first, n, batch_bytes, threads, false, false, &pat, pattern_len, nullptr, out);
+}
+
+int ppg_cursor_open_filter(ppg_ctx *ctx, const ppg_index *ix, const char *gz_path, int32_t first, int32_t n,
+                           int64_t batch_bytes, int threads, const uint8_t *pattern, int32_t pattern_len,
+                           const void *filter, ppg_cursor **out) {
+    PpgSeqPattern pat;
+    if (!seqquery_pattern(pattern, pattern_len, &pat) || (filter && ppg_read_filter_check(filter) != PPG_OK))
+        return PPG_ARG_ERROR;
+    return cursor_open(ctx, ix, gz_path, first, n, batch_bytes, threads, false, false, &pat, pattern_len, filter, out);
+}
+
+int ppg_cursor_filter_result(const ppg_cursor *c, void *result) {
+    if (!c || !c->filter || !c->cur || !result) return PPG_ARG_ERROR;
+    readfilter_outputs(&c->cur->sh, nullptr, result);
+    return PPG_OK;
 }
 
 int ppg_cursor_selected(const ppg_cursor *c, uint8_t **bytes, uint32_t **desc, int64_t *records, int64_t *nbytes) {

@@ -100,6 +100,16 @@ struct PpgSeqPattern {
     uint64_t w[8];
 };
 
+// a ppg_read_filter (include/ppgpu.h "read filters") as ppg_rf_decide's kernel argument
+struct PpgReadFilter {
+    int64_t criteria, min_len, max_len, max_other, qual_base, min_mean_milli, low_q, max_low_milli;
+};
+// the read filter's accumulators: the int64 fields of a ppg_read_filter_result in order (records, passed,
+// failed[4], bases, other, qual_bytes, qual_count[256])
+constexpr int kRfAcc = 265;
+// ppg_rf_measure's Quality histogram: one LDS add per run of equal bytes of a lane, or one per byte
+constexpr int kRfHistRuns = 0, kRfHistBytes = 1;
+
 // ppg_sel_copy: the destination bytes one workgroup writes (256 threads x 4 words of 16 B); ppg_sel_place
 // records, per multiple of it inside a batch's destination range, the selected record that holds that byte
 constexpr uint32_t kSelSpan = 16384;

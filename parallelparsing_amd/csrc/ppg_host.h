@@ -214,6 +214,20 @@ struct ppg_shard {
     DevBuf<uint32_t> sq_len, sq_bits;    // sq_bits: a batch's hit bits when the caller gives no mask
     DevBuf<uint64_t> sq_acc;             // records, hits, (unused), count[5] of the run so far
     PinnedBuf sq_host;                   // a ppg_seq_query_result, then hits per chunk: stored by the kernels
+    int64_t sq_total = 0;                // padded bases of the batch the query laid out last (the filter hook reuses it)
+    // ppg_shard_set_readfilter: every batch's records are also measured and filtered (ppg_readfilter.hip);
+    // pass bits and metrics rows at the shard record number, totals carried in rf_acc
+    int rf_on = 0;
+    PpgReadFilter rf_flt = {};
+    uint32_t *rf_mask = nullptr;
+    int64_t rf_rec_cap = 0;
+    uint8_t *rf_metrics = nullptr;
+    int64_t rf_metrics_cap = 0;
+    int rf_written = 0;                  // the last successful run completed the filter (set by shard_run)
+    int rf_hist = kRfHistRuns;           // ppg_rf_measure's histogram variant (tools/readfilter_probe.py times both)
+    DevBuf<uint64_t> rf_rsc;             // scratch: other | low << 32 and qsum of one batch's records
+    DevBuf<uint64_t> rf_acc;             // kRfAcc accumulators of the run so far
+    PinnedBuf rf_host;                   // a ppg_read_filter_result, then passes per chunk: stored by the kernels
     // ppg_shard_set_select: every batch's selected records are also appended to these buffers
     // (ppg_seqselect.hip), output records and bytes continuing from the batches before
     int sel_on = 0;
@@ -287,6 +301,13 @@ int shard_seq_pack(ppg_shard *sh, int32_t b0, int32_t b1, const uint32_t *recs, 
 int shard_seq_query(ppg_shard *sh, int32_t b0, int32_t b1, const uint32_t *recs, int64_t rec0, int64_t tot,
                     const PpgSeqPattern &pat, int32_t m, uint32_t *mask, bool first);
 bool seqquery_pattern(const uint8_t *pattern, int32_t m, PpgSeqPattern *pat);
+// read filter of chunks [b0, b1) of one resident batch, with the arguments of shard_seq_query; mask and
+// metrics may be null (metrics: row 0 of the plane).  laid_out: a shard_seq_query of the same chunks has
+// just run, its layout (sp_cbase, sq_off, sq_len, sq_total) is used; else the call lays the batch out
+// itself, which blocks.  The totals so far and the chunks' passes are in rf_host once the stream has drained.
+int shard_read_filter(ppg_shard *sh, int32_t b0, int32_t b1, const uint32_t *recs, int64_t rec0, int64_t tot,
+                      const PpgReadFilter &flt, uint32_t *mask, uint8_t *metrics, bool first, bool laid_out);
+void readfilter_outputs(const ppg_shard *sh, int64_t *chunk_passed, void *result);
 // record selection of chunks [b0, b1) of one resident batch (recs: the batch's first descriptor; record j
 // of the batch has bit bit0 + j of mask, a null mask selects all).  sizes: the selected records and their
 // bytes (blocks on the shard's stream).  move: after sizes of the same chunks, queues the selection into

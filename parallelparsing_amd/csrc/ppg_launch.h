@@ -91,6 +91,20 @@ PPG_WEAK hipError_t ppg_launch_seq_query_chunks(hipStream_t s, const PpgInflateR
                                                 uint64_t *acc, int64_t *host_chunk_hits, int n);
 PPG_WEAK hipError_t ppg_launch_seq_query_totals(hipStream_t s, const uint64_t *acc, int64_t *host_result);
 
+// ---- ppg_readfilter.hip ----
+// Weak for the same reason (readfilter_linked, ppg_api.cpp).
+PPG_WEAK hipError_t ppg_launch_rf_measure(hipStream_t s, const uint8_t *out, const PpgInflateJob *jobs,
+                                          const uint8_t *offs, const PpgOffsetRef *oref, const PpgParseInfo *info,
+                                          const uint64_t *base, const uint32_t *recs, const uint64_t *cbase,
+                                          const int64_t *seq_off, const uint32_t *seq_len, uint64_t total, uint32_t thr,
+                                          uint64_t *rsc, uint64_t *acc, int n, int hist);
+PPG_WEAK hipError_t ppg_launch_rf_decide(hipStream_t s, const uint8_t *out, const PpgInflateJob *jobs,
+                                         const PpgInflateResult *ires, const uint8_t *offs, const PpgOffsetRef *oref,
+                                         const PpgParseInfo *info, const uint64_t *base, const uint32_t *recs,
+                                         const uint64_t *rsc, const PpgReadFilter *f, uint32_t *words, uint64_t rec0,
+                                         uint8_t *metrics, uint64_t *acc, int64_t *host_chunk_passed, int n);
+PPG_WEAK hipError_t ppg_launch_rf_totals(hipStream_t s, const uint64_t *acc, int64_t *host_result);
+
 // ---- ppg_seqselect.hip ----
 // Weak for the same reason (select_linked, ppg_api.cpp).
 PPG_WEAK hipError_t ppg_launch_sel_count(hipStream_t s, const PpgInflateResult *ires, const PpgParseInfo *info,
