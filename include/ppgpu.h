@@ -428,7 +428,7 @@ int ppg_shard_select_ready(ppg_shard *sh, int64_t *records, int64_t *bytes);
  *  ppg_shard_set_readfilter    any number of batches: from the next run on every batch is measured
  *                              while its output is resident, record numbers and totals carried across
  *                              batches.  The filter is copied at the call; a NULL filter turns it off.
- *                              A batch's hooks run in the order keys, pack, query, filter, select: a
+ *                              A batch's hooks run in the order keys, pack, query, filter, trim, select: a
  *                              filter with AND_MASK on the query hook's mask sees this batch's hit
  *                              bits, and the select hook sees the product.  A run with more records
  *                              than a cap fails with PPG_BUF_ERROR.
@@ -458,6 +458,90 @@ int ppg_shard_filter_reads(ppg_shard *sh, const void *filter, uint32_t *dev_pass
 int ppg_shard_set_readfilter(ppg_shard *sh, const void *filter, uint32_t *dev_pass_mask, int64_t rec_cap,
                              void *dev_metrics, int64_t metrics_cap);
 int ppg_shard_readfilter_ready(ppg_shard *sh, int64_t *chunk_passed, void *result);
+
+/* ---- read trimming: the usable window of every record, and the keep bit it gives ----
+ * Between "find the reads" and "drop what is too short" every FASTQ pipeline trims: it cuts low-quality
+ * ends and the 3' adapter.  A trimmed read is a window (start, len) into the Sequence and Quality slices;
+ * no text is rebuilt.  S_j, L_j, Q_j, Lq_j are those of "read filters" above.  The quality byte of base i
+ * is qb(i) = Q_j[i] for i < Lq_j and 0 otherwise (the packed reads' zero-filled qual plane): a base
+ * without a Quality byte is below every threshold above 0.
+ * A trim is a ppg_read_trim: twelve int64_t and 64 adapter bytes, 160 bytes, passed as const void *.
+ * ops is a set of bits: PPG_TRIM_LEADING 1, PPG_TRIM_TRAILING 2, PPG_TRIM_WINDOW 4, PPG_TRIM_ADAPTER 8,
+ * PPG_TRIM_AND_MASK 0x100.  head, tail and min_len always apply (0: no effect).  In signed 64-bit integers:
+ *   fixed     b0 = min(head, L_j), e0 = max(b0, L_j - tail).
+ *   Every cut below is decided on [b0, e0) on its own: the cuts do not see each other's results, so all
+ *   of them are one pass of min / max reductions.  This differs from tools that apply their steps one
+ *   after another (a sliding window there sees the text an adapter cut has already shortened).
+ *   LEADING   lead = the least i in [b0, e0) with qb(i) >= qual_base + lead_q; e0 when there is none.
+ *             Off: b0.
+ *   TRAILING  trail = 1 + the greatest i in [b0, e0) with qb(i) >= qual_base + trail_q; b0 when there is
+ *             none.  Off: e0.
+ *   WINDOW    W = win_size.  win = the least i with b0 <= i and i + W <= e0 whose full window has a mean
+ *             below win_q: sum over t < W of qb(i + t) < W * (qual_base + win_q); e0 when no full window
+ *             fails, which includes e0 - b0 < W.  Off: e0.
+ *   ADAPTER   m = adapter_len, A = adapter[0, m).  For p in [b0, e0): ov(p) = min(m, e0 - p) and mis(p) =
+ *             the number of t < ov(p) with S_j[p + t] != A[t], bytes compared as they are (an 'N' of the
+ *             read is a mismatch).  adapt = the least p with ov(p) >= min_overlap and
+ *             1000 * mis(p) <= max_err_milli * ov(p); e0 when there is none.  Off: e0.  Leftmost wins,
+ *             no insertions or deletions: a 3' adapter that may be cut short by the end of the read.
+ *   combine   b = max(b0, lead), e = min(trail, win, adapt), len_j = max(e - b, 0), start_j = b when
+ *             len_j > 0 and 0 otherwise.
+ * The trimmed read is S_j[start_j, start_j + len_j) with the quality Q_j[start_j, min(start_j + len_j, Lq_j)).
+ * keep_j = chunk k's status is 0 and len_j >= min_len.  A failed chunk contributes rows of zeros, no
+ * keeps and nothing to the totals; records the reference parses twice count twice, as in the
+ * filters.
+ * ppg_read_trim_check is host only: PPG_ARG_ERROR for a NULL trim, unknown ops bits, head, tail or
+ * min_len < 0, qual_base outside [0, 255], an enabled lead_q / trail_q / win_q that is < 0 or has
+ * qual_base + q > 256, WINDOW with win_size outside [1, 32], ADAPTER with adapter_len outside [1, 64], a
+ * '\n' among the adapter's bytes, min_overlap outside [1, adapter_len] or max_err_milli outside
+ * [0, 1000]; PPG_OK otherwise.  Every entry point below applies it.
+ * dev_trim (optional): caller device memory, 8-byte aligned, trim_cap rows of two uint32: row j =
+ * (start_j, len_j).  dev_keep_mask (optional): the hit-mask format under the rules of a filter's
+ * dev_pass_mask: without AND_MASK every word below ceil(records / 32) is written whole, pad bits 0,
+ * nothing at or past rec_cap / 32; with AND_MASK a mask is required, bit j becomes old & keep_j and no
+ * other bit changes.  chunk_kept (optional): host int64[n].  `result` (optional) points at a
+ * ppg_read_trim_result: trimmed counts the records of decoded chunks whose window is not (0, L_j); cut[c]
+ * the records that the fixed cut (b0 > 0 or e0 < L_j), LEADING (lead > b0), TRAILING (trail < e0), WINDOW
+ * (win < e0) and ADAPTER (adapt < e0) moved, each on its own.  records > rec_cap (with a mask) or >
+ * trim_cap (with rows): PPG_BUF_ERROR, nothing written.  Every output is a function of the text and the
+ * struct alone.
+ *  ppg_shard_trim_reads      a one-batch shard after its run, blocking; PPG_ARG_ERROR as for
+ *                            ppg_shard_filter_reads.
+ *  ppg_shard_set_readtrim    the hook, as ppg_shard_set_readfilter: the struct is copied at the call, a
+ *                            NULL trim turns it off.  A batch's hooks run in the order keys, pack, query,
+ *                            filter, trim, select: a trim with AND_MASK on the query's mask gives the
+ *                            selection "hit, passes, and still min_len long after trimming".
+ *  ppg_shard_readtrim_ready  as ppg_shard_readfilter_ready. */
+typedef struct {
+    int64_t ops;             /* PPG_TRIM_* bits */
+    int64_t head;            /* bases cut from the 5' end */
+    int64_t tail;            /* bases cut from the 3' end */
+    int64_t qual_base;       /* the Quality byte of quality 0 (33 for Sanger / Illumina 1.8+) */
+    int64_t lead_q;          /* LEADING: the first base of at least this quality starts the read */
+    int64_t trail_q;         /* TRAILING: the last base of at least this quality ends it */
+    int64_t win_size;        /* WINDOW: bases per window, 1 .. 32 */
+    int64_t win_q;           /* ... whose mean quality must not fall below this */
+    int64_t min_overlap;     /* ADAPTER: the least overlap that counts */
+    int64_t max_err_milli;   /* ... and 1000 x the largest fraction of mismatches in it */
+    int64_t min_len;         /* keep: the least trimmed length */
+    int64_t adapter_len;
+    uint8_t adapter[64];
+} ppg_read_trim;
+typedef struct {
+    int64_t records;         /* records trimmed */
+    int64_t kept;
+    int64_t trimmed;         /* window != (0, L_j) */
+    int64_t cut[5];          /* fixed, LEADING, TRAILING, WINDOW, ADAPTER */
+    int64_t bases;           /* sum of L_j */
+    int64_t bases_window;    /* sum of len_j */
+    int64_t bases_kept;      /* sum of len_j over the kept records */
+} ppg_read_trim_result;
+int ppg_read_trim_check(const void *trim);
+int ppg_shard_trim_reads(ppg_shard *sh, const void *trim, uint32_t *dev_keep_mask, int64_t rec_cap, void *dev_trim,
+                         int64_t trim_cap, int64_t *chunk_kept, void *result);
+int ppg_shard_set_readtrim(ppg_shard *sh, const void *trim, uint32_t *dev_keep_mask, int64_t rec_cap, void *dev_trim,
+                           int64_t trim_cap);
+int ppg_shard_readtrim_ready(ppg_shard *sh, int64_t *chunk_kept, void *result);
 
 /* Device-resident per-chunk record counts (int64[n]) copied to caller device memory on this
  * GPU (the input of the cross-GPU all-gather). */
@@ -569,6 +653,20 @@ int ppg_cursor_open_filter(ppg_ctx *ctx, const ppg_index *ix, const char *gz_pat
                            int64_t batch_bytes, int threads, const uint8_t *pattern, int32_t pattern_len,
                            const void *filter, ppg_cursor **out);
 int ppg_cursor_filter_result(const ppg_cursor *c, void *result);
+
+/* ... and trimmed: the selection is "hit, pass and keep" ("read trimming" above), and every selected
+ * record comes with its window.  A NULL trim is exactly ppg_cursor_open_filter (whose filter may be
+ * NULL as well); the trim is copied at the call and its AND_MASK bit is ignored; a bad one is PPG_ARG_ERROR.
+ *  ppg_cursor_selected_trim  the (start, len) rows of the current batch's selected records, in their
+ *                            order, two uint32 each, in pinned host memory that stays valid until the
+ *                            next ppg_cursor_next.
+ *  ppg_cursor_trim_result    the current batch's ppg_read_trim_result, over all its records.
+ * Both are PPG_ARG_ERROR on other cursors and before the first ppg_cursor_next. */
+int ppg_cursor_open_trim(ppg_ctx *ctx, const ppg_index *ix, const char *gz_path, int32_t first, int32_t n,
+                         int64_t batch_bytes, int threads, const uint8_t *pattern, int32_t pattern_len,
+                         const void *filter, const void *trim, ppg_cursor **out);
+int ppg_cursor_selected_trim(const ppg_cursor *c, uint32_t **trim);
+int ppg_cursor_trim_result(const ppg_cursor *c, void *result);
 
 /* ======================= multi-GPU DecompressAll (one process per GPU) =======================
  * BatchedFASTQ's fan-out (BatchedFASTQ.cs:62-77: a task per chunk) becomes a fan-out over GPUs:

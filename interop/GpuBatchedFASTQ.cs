@@ -16,6 +16,7 @@
 // (Source only: no .NET SDK in this image; tests/test_interop_cs.py checks the externs it uses.)
 using System;
 using System.Collections;
+using System.Collections.Generic;
 using ParallelParsing.Common;
 using ParallelParsing.Interop;
 using Index = ParallelParsing.Common.Index;
@@ -54,6 +55,27 @@ public sealed unsafe class GpuJob : IDisposable
     {
         if (Comm != 0) PpGpu.ppg_comm_free(Comm);
         PpGpu.ppg_close(Ctx);
+    }
+}
+
+/// <summary>A record and the window a read trim left of it: TrimmedSequence = Sequence[start, start + len),
+/// TrimmedQuality = Quality[start, min(start + len, Quality.Length)); slices of the record's own memory.</summary>
+public sealed class TrimmedFastqRecord
+{
+    public FastqRecord Record { get; }
+    public int Start { get; }
+    public int Length { get; }
+    public ReadOnlyMemory<byte> TrimmedSequence { get; }
+    public ReadOnlyMemory<byte> TrimmedQuality { get; }
+
+    public TrimmedFastqRecord(FastqRecord record, Memory<byte> sequence, Memory<byte> quality, int start, int length)
+    {
+        Record = record;
+        Start = start;
+        Length = length;
+        TrimmedSequence = sequence.Slice(start, length);
+        int qa = Math.Min(start, quality.Length), qe = Math.Min(start + length, quality.Length);
+        TrimmedQuality = quality.Slice(qa, qe - qa);
     }
 }
 
@@ -176,6 +198,53 @@ public sealed class GpuBatchedFASTQ : IEnumerable<FastqRecord>, IDisposable
         }
     }
 
+    /// <summary>Where(pattern, filter) with every record trimmed on the GPU as well (low-quality ends, sliding
+    /// window, 3' adapter: PpgReadTrim): only the records that hit, pass and are still MinLen long after
+    /// trimming are brought to the host, each with its window as TrimmedSequence / TrimmedQuality.  A null
+    /// filter applies none.</summary>
+    public IEnumerable<TrimmedFastqRecord> Where(string pattern, PpgReadFilter? filter, PpgReadTrim trim)
+    {
+        var (first, n) = ChunkRange();
+        nint cur = OpenTrim(first, n, System.Text.Encoding.ASCII.GetBytes(pattern), filter, trim);
+        try
+        {
+            while (true)
+            {
+                var recs = NextTrimmed(cur);
+                if (recs == null) yield break;
+                foreach (var r in recs) yield return r;
+            }
+        }
+        finally
+        {
+            PpGpu.ppg_cursor_close(cur);
+        }
+    }
+
+    private unsafe nint OpenTrim(int first, int n, byte[] pat, PpgReadFilter? filter, PpgReadTrim trim)
+    {
+        nint cur;
+        PpgReadFilter f = filter ?? default;
+        fixed (byte* p = pat)
+            PpGpu.Check(PpGpu.ppg_cursor_open_trim(_Ctx, _Ix, _Path, first, n, BatchBytes, _Threads, p, pat.Length,
+                                                   filter.HasValue ? &f : null, &trim, out cur));
+        return cur;
+    }
+
+    // NextSelected with the records' windows: row i of ppg_cursor_selected_trim is (start, len) of record i
+    private static unsafe TrimmedFastqRecord[]? NextTrimmed(nint cur)
+    {
+        var fields = new List<(Memory<byte> Sequence, Memory<byte> Quality)>();
+        var recs = NextSelected(cur, fields);
+        if (recs == null) return null;
+        uint* win;
+        PpGpu.Check(PpGpu.ppg_cursor_selected_trim(cur, &win));
+        var res = new TrimmedFastqRecord[recs.Length];
+        for (int i = 0; i < recs.Length; i++)
+            res[i] = new TrimmedFastqRecord(recs[i], fields[i].Sequence, fields[i].Quality, (int)win[2 * i], (int)win[2 * i + 1]);
+        return res;
+    }
+
     private unsafe nint OpenFilter(int first, int n, byte[] pat, PpgReadFilter filter)
     {
         nint cur;
@@ -196,7 +265,8 @@ public sealed class GpuBatchedFASTQ : IEnumerable<FastqRecord>, IDisposable
 
     // The next batch's selected records, or null after the last batch.  A record's text is copied into a
     // managed array of its own; its descriptor is relative to the record's first byte (start = 0).
-    private static unsafe FastqRecord[]? NextSelected(nint cur)
+    // fields (optional) receives every record's Sequence and Quality memory.
+    private static unsafe FastqRecord[]? NextSelected(nint cur, List<(Memory<byte>, Memory<byte>)>? fields = null)
     {
         int rc = PpGpu.ppg_cursor_next(cur, out _);
         if (rc == (int)ZResult.STREAM_END) return null;
@@ -218,6 +288,7 @@ public sealed class GpuBatchedFASTQ : IEnumerable<FastqRecord>, IDisposable
                 raw.Slice((int)d[0] + 1, (int)(d[1] - d[0] - 1)),
                 raw.Slice((int)d[1] + 2, (int)(d[2] - d[1] - 2)),
                 raw.Slice((int)d[2] + 1, (int)(d[3] - d[2] - 1)));
+            fields?.Add((raw.Slice((int)d[0] + 1, (int)(d[1] - d[0] - 1)), raw.Slice((int)d[2] + 1, (int)(d[3] - d[2] - 1))));
         }
         return recs;
     }

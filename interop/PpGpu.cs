@@ -90,6 +90,37 @@ public unsafe struct PpgReadFilterResult // ppg_read_filter_result
     public fixed long QualCount[256];   // Quality bytes by value
 }
 
+[StructLayout(LayoutKind.Sequential)]
+public unsafe struct PpgReadTrim        // ppg_read_trim
+{
+    public const long Leading = 1, Trailing = 2, Window = 4, Adapter = 8, AndMask = 0x100;
+    public long Ops;                    // the bits above
+    public long Head;                   // bases cut from the 5' end
+    public long Tail;                   // bases cut from the 3' end
+    public long QualBase;               // the Quality byte of quality 0 (33)
+    public long LeadQ;                  // the first base of at least this quality starts the read
+    public long TrailQ;                 // the last base of at least this quality ends it
+    public long WinSize;                // bases per sliding window, 1 .. 32
+    public long WinQ;                   // ... whose mean quality must not fall below this
+    public long MinOverlap;             // the least adapter overlap that counts
+    public long MaxErrMilli;            // 1000 x the largest fraction of mismatches in it
+    public long MinLen;                 // keep: the least trimmed length
+    public long AdapterLen;
+    public fixed byte AdapterBytes[64];
+}
+
+[StructLayout(LayoutKind.Sequential)]
+public unsafe struct PpgReadTrimResult  // ppg_read_trim_result
+{
+    public long Records;
+    public long Kept;
+    public long Trimmed;
+    public fixed long Cut[5];           // fixed, leading, trailing, window, adapter
+    public long Bases;
+    public long BasesWindow;
+    public long BasesKept;
+}
+
 internal static unsafe class PpGpu
 {
     const string Lib = "ppgpu";   // libppgpu.so from parallelparsing_amd/
@@ -183,6 +214,14 @@ internal static unsafe class PpGpu
     [DllImport(Lib)] public static extern int ppg_shard_set_readfilter(nint shard, void* filter, uint* devPassMask,
         long recCap, void* devMetrics, long metricsCap);
     [DllImport(Lib)] public static extern int ppg_shard_readfilter_ready(nint shard, long* chunkPassed, void* result);
+    // read trimming: the window (start, len) of every record and the keep bits (trim: a PpgReadTrim*,
+    // result: a PpgReadTrimResult*; mask and rows are device pointers)
+    [DllImport(Lib)] public static extern int ppg_read_trim_check(void* trim);
+    [DllImport(Lib)] public static extern int ppg_shard_trim_reads(nint shard, void* trim, uint* devKeepMask,
+        long recCap, void* devTrim, long trimCap, long* chunkKept, void* result);
+    [DllImport(Lib)] public static extern int ppg_shard_set_readtrim(nint shard, void* trim, uint* devKeepMask,
+        long recCap, void* devTrim, long trimCap);
+    [DllImport(Lib)] public static extern int ppg_shard_readtrim_ready(nint shard, long* chunkKept, void* result);
     // record selection: the records a mask selects, compacted on the GPU (device pointers; a null mask
     // with maskCap 0 selects every record)
     [DllImport(Lib)] public static extern int ppg_shard_select_size(nint shard, uint* devMask, long maskCap,
@@ -225,6 +264,11 @@ internal static unsafe class PpGpu
     [DllImport(Lib)] public static extern int ppg_cursor_open_filter(nint ctx, nint ix, string gzPath, int first, int n,
         long batchBytes, int threads, byte* pattern, int patternLen, void* filter, out nint cursor);
     [DllImport(Lib)] public static extern int ppg_cursor_filter_result(nint cursor, void* result);
+    // ... and trimmed: "hit, pass and keep", every selected record with its window (null filter / trim: none)
+    [DllImport(Lib)] public static extern int ppg_cursor_open_trim(nint ctx, nint ix, string gzPath, int first, int n,
+        long batchBytes, int threads, byte* pattern, int patternLen, void* filter, void* trim, out nint cursor);
+    [DllImport(Lib)] public static extern int ppg_cursor_selected_trim(nint cursor, uint** trim);
+    [DllImport(Lib)] public static extern int ppg_cursor_trim_result(nint cursor, void* result);
 
     // ---- multi-GPU DecompressAll: partition + count all-gather over RCCL inside the library ----
     [DllImport(Lib)] public static extern int ppg_comm_unique_id(byte* id /* 128 bytes */);

@@ -287,6 +287,27 @@ class FastqRecord:
         return f"FastqRecord({self.identifier!r})"
 
 
+class TrimmedRecord(FastqRecord):
+    """A FastqRecord with the window a read trim left of it (include/ppgpu.h "read trimming"):
+    trimmed_sequence = Sequence[start, start + len), trimmed_quality = Quality[start, start + len)."""
+
+    __slots__ = ("trim_start", "trim_len")
+
+    def __init__(self, raw, start, n1, n2, n3, n4, trim_start, trim_len):
+        super().__init__(raw, start, n1, n2, n3, n4)
+        self.trim_start, self.trim_len = trim_start, trim_len
+
+    @property
+    def trimmed_sequence(self):
+        a = self.n1 + 1 + self.trim_start
+        return bytes(self.raw[a:a + self.trim_len])
+
+    @property
+    def trimmed_quality(self):
+        a = self.n3 + 1 + self.trim_start
+        return bytes(self.raw[a:min(a + self.trim_len, self.n4)])
+
+
 def records_from_descriptors(raw, desc):
     """FastqRecords of one chunk from its (n,4) uint32 descriptors over raw = offset ++ chunk."""
     recs = []
@@ -692,16 +713,123 @@ class ReadFilterResult:
                 f"bases={self.bases}, other={self.other}, qual_bytes={self.qual_bytes})")
 
 
+class ReadTrim:
+    """A read trim (include/ppgpu.h "read trimming"); a cut left at None is not applied.  head / tail
+    bases are cut from the ends in any case; leading_quality / trailing_quality cut the bases below that
+    quality from the 5' / 3' end; window=(size, quality) cuts from the first full window whose mean quality
+    is below `quality`; adapter (bytes) cuts from the leftmost 3' adapter site of at least min_overlap
+    bases with at most max_error_rate mismatches (held as round(1000 * x), compared as exact integers).
+    Every cut is decided on the read after head / tail alone, not on the others' results.  A read is
+    kept when min_length bases are left."""
+
+    def __init__(self, head=0, tail=0, leading_quality=None, trailing_quality=None, window=None, adapter=None,
+                 min_overlap=3, max_error_rate=0.1, min_length=0, quality_base=33):
+        if window is not None and len(tuple(window)) != 2:
+            raise ValueError("ReadTrim: window is (size, quality)")
+        self.head, self.tail = head, tail
+        self.leading_quality, self.trailing_quality = leading_quality, trailing_quality
+        self.window = None if window is None else tuple(window)
+        self.adapter = None if adapter is None else (adapter.encode("ascii") if isinstance(adapter, str) else bytes(adapter))
+        self.min_overlap, self.max_error_rate = min_overlap, max_error_rate
+        self.min_length, self.quality_base = min_length, quality_base
+
+    def struct(self, and_mask=False):
+        """The ppg_read_trim of this trim (and_mask: with the AND_MASK bit); ValueError when
+        ppg_read_trim_check refuses it."""
+        ops = 0
+        if self.leading_quality is not None:
+            ops |= _lib.PPG_TRIM_LEADING
+        if self.trailing_quality is not None:
+            ops |= _lib.PPG_TRIM_TRAILING
+        if self.window is not None:
+            ops |= _lib.PPG_TRIM_WINDOW
+        if self.adapter is not None:
+            ops |= _lib.PPG_TRIM_ADAPTER
+        if and_mask:
+            ops |= _lib.PPG_TRIM_AND_MASK
+        ad = self.adapter or b""
+        if len(ad) > 64:
+            raise ValueError("ReadTrim: an adapter has at most 64 bytes")
+        t = _lib.PpgReadTrim(
+            ops, int(self.head), int(self.tail), int(self.quality_base),
+            0 if self.leading_quality is None else int(self.leading_quality),
+            0 if self.trailing_quality is None else int(self.trailing_quality),
+            0 if self.window is None else int(self.window[0]), 0 if self.window is None else int(self.window[1]),
+            int(self.min_overlap) if self.adapter is not None else 0,
+            int(round(1000 * self.max_error_rate)) if self.adapter is not None else 0,
+            int(self.min_length), len(ad), (C.c_uint8 * 64)(*ad))
+        if lib.ppg_read_trim_check(C.byref(t)) != 0:
+            raise ValueError(f"ReadTrim: not a valid trim: {self!r}")
+        return t
+
+    def __repr__(self):
+        return (f"ReadTrim(head={self.head}, tail={self.tail}, leading_quality={self.leading_quality}, "
+                f"trailing_quality={self.trailing_quality}, window={self.window}, adapter={self.adapter!r}, "
+                f"min_overlap={self.min_overlap}, max_error_rate={self.max_error_rate}, min_length={self.min_length}, "
+                f"quality_base={self.quality_base})")
+
+
+def _trim_struct(trim, and_mask=False):
+    """The ppg_read_trim of a ReadTrim, or a _lib.PpgReadTrim as it is (its AND_MASK bit set on demand)."""
+    if isinstance(trim, ReadTrim):
+        return trim.struct(and_mask)
+    if not isinstance(trim, _lib.PpgReadTrim):
+        raise ValueError("expected a ReadTrim")
+    t = _lib.PpgReadTrim.from_buffer_copy(trim)
+    if and_mask:
+        t.ops |= _lib.PPG_TRIM_AND_MASK
+    return t
+
+
+class ReadTrimResult:
+    """The result of a read trim (include/ppgpu.h "read trimming"): `records`, `kept`, `trimmed` (records
+    whose window is not the whole read), `cut` (records each cut moved on its own, by 'fixed', 'leading',
+    'trailing', 'window', 'adapter'), `bases`, `bases_window`, `bases_kept`, `chunk_kept` (numpy int64,
+    keeps per chunk) and, when asked for, `windows` (an int32 CUDA tensor [records, 2] of (start, len)
+    rows) and `keep_mask` (a uint32 CUDA tensor in the hit-mask format)."""
+
+    CUTS = ("fixed", "leading", "trailing", "window", "adapter")
+
+    def __init__(self, result, chunk_kept=None, keep_mask=None, windows=None):
+        self.records, self.kept, self.trimmed = int(result.records), int(result.kept), int(result.trimmed)
+        self.cut = {c: int(v) for c, v in zip(self.CUTS, result.cut)}
+        self.bases, self.bases_window, self.bases_kept = int(result.bases), int(result.bases_window), int(result.bases_kept)
+        self.chunk_kept = chunk_kept
+        self.keep_mask = keep_mask
+        self.windows = windows
+
+    def keep_records(self):
+        """The shard record numbers of the set mask bits, ascending: an int64 tensor on the mask's device."""
+        if self.keep_mask is None:
+            raise ValueError("ReadTrimResult.keep_records: the trim was run without a mask")
+        import torch
+        w = self.keep_mask.view(torch.int32)[:(self.records + 31) // 32]
+        bit = torch.arange(32, dtype=torch.int32, device=w.device)
+        return ((w[:, None] >> bit) & 1).reshape(-1).nonzero().reshape(-1)
+
+    def windows_host(self):
+        """The (start, len) rows of the records as a numpy uint32[records, 2] array."""
+        if self.windows is None:
+            raise ValueError("ReadTrimResult.windows_host: the trim was run without windows")
+        return self.windows.reshape(-1, 2)[:self.records].cpu().numpy().view(np.uint32).reshape(-1, 2)
+
+    def __repr__(self):
+        return (f"ReadTrimResult(records={self.records}, kept={self.kept}, trimmed={self.trimmed}, cut={self.cut}, "
+                f"bases={self.bases}, bases_window={self.bases_window}, bases_kept={self.bases_kept})")
+
+
 class SelectedRecords:
     """The records a mask selects (include/ppgpu.h "record selection"): `bytes` (uint8, the selected
     records' text back to back), `sel_off` (int64, records + 1 offsets into it), `desc` (records x 4:
     the newline positions relative to the record's own first byte) and `recno` (int64, the records'
     numbers), with `records` and `nbytes` the counts in use.  The arrays are either CUDA tensors on
     one device (uint8, int64, int32 views of the uint32 descriptors) or numpy arrays (uint8, int64,
-    uint32); record(i) and iteration read host arrays."""
+    uint32); record(i) and iteration read host arrays.  A trimming cursor's selection also has `trim`,
+    a numpy uint32[records, 2] array of the records' (start, len) windows (else None), and trimmed(i)."""
 
-    def __init__(self, bytes, sel_off, desc, recno, records=None, nbytes=None):   # noqa: A002
+    def __init__(self, bytes, sel_off, desc, recno, records=None, nbytes=None, trim=None):   # noqa: A002
         self.bytes, self.sel_off, self.desc, self.recno = bytes, sel_off, desc, recno
+        self.trim = trim
         self.records = int(records) if records is not None else int(recno.shape[0])
         self.nbytes = int(nbytes) if nbytes is not None else int(bytes.shape[0])
 
@@ -767,6 +895,15 @@ class SelectedRecords:
         a, e = int(self.sel_off[i]), int(self.sel_off[i + 1])
         n1, n2, n3, n4 = (int(v) for v in self.desc[i])
         return FastqRecord(self.bytes[a:e], 0, n1, n2, n3, n4)
+
+    def trimmed(self, i):
+        """(sequence, quality) of selected record i cut to its window: views of this selection's bytes,
+        S[start, start + len) and Q[start, min(start + len, Lq)) (include/ppgpu.h "read trimming")."""
+        if self.trim is None:
+            raise ValueError("SelectedRecords: trimmed() needs a selection made with a trim")
+        r = self.record(i)
+        a, n = int(self.trim[i][0]), int(self.trim[i][1])
+        return r.raw[r.n1 + 1 + a:r.n1 + 1 + a + n], r.raw[r.n3 + 1 + a:min(r.n3 + 1 + a + n, r.n4)]
 
     def __len__(self):
         return self.records
@@ -839,7 +976,8 @@ class Shard:
 
     def run(self):
         hooked = getattr(self, "_seqpack", None) is not None or getattr(self, "_sq_mask", None) is not None or \
-            getattr(self, "_select", None) is not None or getattr(self, "_rf", None) is not None
+            getattr(self, "_select", None) is not None or getattr(self, "_rf", None) is not None or \
+            getattr(self, "_rt", None) is not None
         if self._on_device or hooked:
             self._torch_order()   # the caller may have rewritten comp (or the hooks' tensors) since the last run
         check(lib.ppg_shard_run(self._h), "DecompressAll")
@@ -1054,6 +1192,69 @@ class Shard:
             return None
         rf = getattr(self, "_rf", None) or (None, None)
         return ReadFilterResult(res, ch, rf[0], rf[1])
+
+    def trim_reads(self, trim, mask=False, windows=True):
+        """The read trim `trim` (a ReadTrim) over the records of a one-batch shard after its run
+        (ppg_shard_trim_reads), as a ReadTrimResult.  windows=True also returns the per-record (start,
+        len) rows as an int32 CUDA tensor [records, 2]; mask=True the keep bits as a uint32 CUDA tensor;
+        a tensor of hit-mask words instead is ANDed in place with them.  Ordered after torch's stream,
+        complete on return."""
+        import torch
+        dev = torch.device("cuda", self.dev.device)
+        nrec = max(self.total_records, 0)
+        km, cap, and_mask = None, 0, False
+        if mask is True:
+            cap = (nrec + 31) // 32 * 32
+            km = torch.zeros(cap // 32, dtype=torch.int32, device=dev).view(torch.uint32)
+        elif mask is not False and mask is not None:
+            _, cap, km = _mask_arg(mask, "trim_reads")
+            and_mask = True
+        rows = torch.zeros((nrec, 2), dtype=torch.int32, device=dev) if windows else None
+        t = _trim_struct(trim, and_mask)
+        self._torch_order()
+        res, ch = _lib.PpgReadTrimResult(), np.zeros(self.n, np.int64)
+        check(lib.ppg_shard_trim_reads(self._h, C.byref(t), C.c_void_p(km.data_ptr()) if cap else None, cap,
+                                       C.c_void_p(rows.data_ptr()) if windows and nrec else None, nrec if windows else 0,
+                                       _ptr(ch), C.byref(res)), "trim_reads")
+        return ReadTrimResult(res, ch, km, rows)
+
+    def set_readtrim(self, trim, mask=None, windows=None, and_mask=False):
+        """From the next run on, every output batch is trimmed by `trim` while its output is resident
+        (ppg_shard_set_readtrim): works for shards of any number of batches, and runs after the
+        set_seqquery and set_readfilter hooks and before a set_select hook; the result is `readtrim`
+        after the run.  mask: an int32 / uint32 CUDA tensor of at least ceil(records / 32) words for the
+        keep bits (and_mask=True: its bits are ANDed with them instead); windows: an int32 / uint32 CUDA
+        tensor of at least 2 * records words for the (start, len) rows.  trim=None turns it off."""
+        if trim is None:
+            check(lib.ppg_shard_set_readtrim(self._h, None, None, 0, None, 0), "set_readtrim")
+            self._rt = None
+            return self
+        import torch
+        ptr, cap = None, 0
+        if mask is not None:
+            ptr, cap, mask = _mask_arg(mask, "set_readtrim")
+            if mask is not None:
+                mask = mask.view(torch.uint32)
+        wptr, wcap = None, 0
+        if windows is not None:
+            if not (windows.is_cuda and windows.dtype in (torch.int32, torch.uint32) and windows.is_contiguous()):
+                raise ValueError("set_readtrim: windows must be a contiguous int32 / uint32 CUDA tensor")
+            wcap = windows.numel() // 2
+            wptr = C.c_void_p(windows.data_ptr()) if wcap else None
+        t = _trim_struct(trim, and_mask)
+        self._rt = (mask, windows)   # kept alive while the library may write them
+        self._torch_order()
+        check(lib.ppg_shard_set_readtrim(self._h, C.byref(t), ptr, cap, wptr, wcap), "set_readtrim")
+        return self
+
+    @property
+    def readtrim(self):
+        """The ReadTrimResult of the last run's set_readtrim hook, or None when that run did not complete one."""
+        res, ch = _lib.PpgReadTrimResult(), np.zeros(self.n, np.int64)
+        if lib.ppg_shard_readtrim_ready(self._h, _ptr(ch), C.byref(res)) != 1:
+            return None
+        rt = getattr(self, "_rt", None) or (None, None)
+        return ReadTrimResult(res, ch, rt[0], rt[1])
 
     def select_size(self, mask=None):
         """(records, bytes) a selection by `mask` holds, after a run of any number of batches
@@ -1289,13 +1490,18 @@ class Cursor:
 
     filter=ReadFilter(...) (ppg_cursor_open_filter; alone or with pattern=, not with packed=True) narrows
     that selection to the hits that pass the filter, decided on the GPU as well; Batch.filter_result is
-    then the batch's ReadFilterResult, over all its records."""
+    then the batch's ReadFilterResult, over all its records.
+
+    trim=ReadTrim(...) (ppg_cursor_open_trim; alone or with pattern= / filter=, not with packed=True) trims
+    every record on the GPU, narrows the selection to the records that are still min_length long, and
+    hands out the windows: Batch.selected.trim and .trimmed(i); Batch.trim_result is the batch's
+    ReadTrimResult, over all its records."""
 
     def __init__(self, index, gzip_path, first=0, n=None, batch_bytes=1 << 30, threads=8, device=None,
-                 packed=False, quality=True, pattern=None, filter=None):   # noqa: A002
-        if packed and (pattern is not None or filter is not None):
-            raise ValueError("Cursor: packed=True and pattern= / filter= exclude each other")
-        if filter is not None and pattern is None:
+                 packed=False, quality=True, pattern=None, filter=None, trim=None):   # noqa: A002
+        if packed and (pattern is not None or filter is not None or trim is not None):
+            raise ValueError("Cursor: packed=True and pattern= / filter= / trim= exclude each other")
+        if (filter is not None or trim is not None) and pattern is None:
             pattern = b""
         self.index = index
         self.dev = device or Device.default()
@@ -1304,8 +1510,16 @@ class Cursor:
         self.packed, self.quality = bool(packed), bool(quality)
         self.select = pattern is not None
         self.filtered = filter is not None
+        self.trimming = trim is not None
         h = C.c_void_p()
-        if self.filtered:
+        if self.trimming:
+            pat, m = _pattern_arg(pattern)
+            f = _filter_struct(filter) if self.filtered else None
+            t = _trim_struct(trim)
+            check(lib.ppg_cursor_open_trim(self.dev.handle, index.handle, os.fsencode(gzip_path), int(first), int(n),
+                                           int(batch_bytes), int(threads), pat, m, C.byref(f) if self.filtered else None,
+                                           C.byref(t), C.byref(h)), "ppg_cursor_open_trim")
+        elif self.filtered:
             pat, m = _pattern_arg(pattern)
             f = _filter_struct(filter)
             check(lib.ppg_cursor_open_filter(self.dev.handle, index.handle, os.fsencode(gzip_path), int(first), int(n),
@@ -1346,7 +1560,14 @@ class Cursor:
             return None
         check(rc, "ppg_cursor_next")
         return Batch(b, self.packed_reads(b.nrecords) if self.packed else None,
-                     self.selected_records() if self.select else None, self.filter_result() if self.filtered else None)
+                     self.selected_records() if self.select else None, self.filter_result() if self.filtered else None,
+                     self.trim_result() if self.trimming else None)
+
+    def trim_result(self):
+        """The current batch's ReadTrimResult (ppg_cursor_trim_result): totals alone."""
+        res = _lib.PpgReadTrimResult()
+        check(lib.ppg_cursor_trim_result(self._h, C.byref(res)), "ppg_cursor_trim_result")
+        return ReadTrimResult(res)
 
     def filter_result(self):
         """The current batch's ReadFilterResult (ppg_cursor_filter_result): totals alone."""
@@ -1357,7 +1578,8 @@ class Cursor:
     def selected_records(self):
         """The current batch's selection (ppg_cursor_selected / ppg_cursor_selected_index) as a host
         SelectedRecords: bytes and desc are views of pinned memory, valid until the next batch; sel_off
-        (batch-relative) and recno (among the records this cursor hands out) are copies."""
+        (batch-relative) and recno (among the records this cursor hands out) are copies; with a trim,
+        trim is a view of pinned memory as well (ppg_cursor_selected_trim)."""
         pb, pd = C.c_void_p(), C.c_void_p()
         rec, nb = C.c_int64(), C.c_int64()
         check(lib.ppg_cursor_selected(self._h, C.byref(pb), C.byref(pd), C.byref(rec), C.byref(nb)), "ppg_cursor_selected")
@@ -1370,7 +1592,13 @@ class Cursor:
                 return np.zeros(0, ct)
             return np.ctypeslib.as_array(C.cast(p, C.POINTER(ct)), (n,))
 
-        return SelectedRecords(view(pb, C.c_uint8, nb), off, view(pd, C.c_uint32, 4 * nr).reshape(-1, 4), recno[:nr], nr, nb)
+        trim = None
+        if self.trimming:
+            pt = C.c_void_p()
+            check(lib.ppg_cursor_selected_trim(self._h, C.byref(pt)), "ppg_cursor_selected_trim")
+            trim = view(pt, C.c_uint32, 2 * nr).reshape(-1, 2)
+        return SelectedRecords(view(pb, C.c_uint8, nb), off, view(pd, C.c_uint32, 4 * nr).reshape(-1, 4), recno[:nr], nr, nb,
+                               trim)
 
     def packed_reads(self, nrecords):
         """The current batch's planes (ppg_cursor_packed / ppg_cursor_packed_offsets) as a host
@@ -1404,9 +1632,9 @@ class Batch:
     """One ppg_batch: text (uint8), raw_off / rec_off (int64, nchunks + 1), desc (nrecords x 4).  A
     packed cursor's batch has text = desc = None and `packed`, a host PackedReads; a select cursor's
     has text = desc = None and `selected`, a host SelectedRecords, and with a filter `filter_result`, the
-    batch's ReadFilterResult."""
+    batch's ReadFilterResult, with a trim `trim_result`, its ReadTrimResult."""
 
-    def __init__(self, b, packed=None, selected=None, filter_result=None):
+    def __init__(self, b, packed=None, selected=None, filter_result=None, trim_result=None):
         self.first_chunk, self.nchunks = b.first_chunk, b.nchunks
         self.record_base, self.nrecords = b.record_base, b.nrecords
         self.raw_off = np.ctypeslib.as_array(b.raw_off, (b.nchunks + 1,))
@@ -1414,6 +1642,7 @@ class Batch:
         self.packed = packed
         self.selected = selected
         self.filter_result = filter_result
+        self.trim_result = trim_result
         if packed is not None or selected is not None or not b.text:
             self.text = self.desc = None
             return
@@ -1512,24 +1741,30 @@ class BatchedFASTQ:
         finally:
             cur.close()
 
-    def Where(self, pattern=None, filter=None):   # noqa: A002
+    def Where(self, pattern=None, filter=None, trim=None):   # noqa: A002
         """The records whose Sequence contains `pattern` (the body of Benchmark/Naive.cs RunPattern's
         loop: foreach record, if record.Sequence.Contains(pattern)), in canonical order, through the
         select cursor (ppg_cursor_open_select) over chunk_range(): searched and compacted on the GPU,
         only the hits reach the host.  Each batch's bytes are copied out before the next one is
         requested.  pattern as in CountPattern (None or b"": every record).  filter: a ReadFilter the
-        records must pass as well (ppg_cursor_open_filter), decided on the GPU too."""
+        records must pass as well (ppg_cursor_open_filter), decided on the GPU too.  trim: a ReadTrim
+        (ppg_cursor_open_trim): the records are trimmed on the GPU, those shorter than its min_length
+        afterwards are dropped, and the rest come as TrimmedRecord with trimmed_sequence / trimmed_quality."""
         first, n = self.chunk_range()
         cur = Cursor(self.index, self.gzip_path, first=first, n=n, batch_bytes=self.batch_bytes,
                      threads=16 if self.enable_ssd_optimization else 8, device=self.dev,
-                     pattern=b"" if pattern is None else pattern, filter=filter)
+                     pattern=b"" if pattern is None else pattern, filter=filter, trim=trim)
         try:
             for b in cur:
                 sel = b.selected
                 raw = sel.bytes.tobytes()
                 off, desc = sel.sel_off.tolist(), sel.desc.tolist()
+                win = sel.trim.tolist() if trim is not None else None
                 for i in range(sel.records):
-                    yield FastqRecord(raw[off[i]:off[i + 1]], 0, *desc[i])
+                    if win is None:
+                        yield FastqRecord(raw[off[i]:off[i + 1]], 0, *desc[i])
+                    else:
+                        yield TrimmedRecord(raw[off[i]:off[i + 1]], 0, *desc[i], *win[i])
         finally:
             cur.close()
 
@@ -1554,13 +1789,19 @@ class BatchedFASTQ:
         return sh
 
     def _query(self, pattern):
-        return self._query_shard().set_readfilter(None).set_seqquery(pattern).run().seqquery
+        return self._query_shard().set_readfilter(None).set_readtrim(None).set_seqquery(pattern).run().seqquery
 
     def CountPassing(self, filter):   # noqa: A002
         """The ReadFilterResult of `filter` (a ReadFilter) over the file: how many records pass, how many
         fail each criterion, and the totals, measured on the GPU batch by batch (Shard.set_readfilter):
         no record text reaches the host."""
-        return self._query_shard().set_seqquery(None).set_readfilter(filter).run().readfilter
+        return self._query_shard().set_seqquery(None).set_readtrim(None).set_readfilter(filter).run().readfilter
+
+    def CountTrimmed(self, trim):
+        """The ReadTrimResult of `trim` (a ReadTrim) over the file: how many records each cut moves, how
+        many are kept and the bases left, measured on the GPU batch by batch (Shard.set_readtrim): totals
+        alone, no record text and no window reaches the host."""
+        return self._query_shard().set_seqquery(None).set_readfilter(None).set_readtrim(trim).run().readtrim
 
     def QualityCounts(self):
         """numpy int64[256]: the bytes of every Quality line by value, counted on the GPU batch by batch."""

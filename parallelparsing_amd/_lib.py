@@ -130,6 +130,13 @@ _SIGS = {
     "ppg_shard_readfilter_ready": (C.c_int, [vp, vp, vp]),
     "ppg_cursor_open_filter": (C.c_int, [vp, vp, C.c_char_p, i32, i32, i64, C.c_int, vp, i32, vp, P(vp)]),
     "ppg_cursor_filter_result": (C.c_int, [vp, vp]),
+    "ppg_read_trim_check": (C.c_int, [vp]),
+    "ppg_shard_trim_reads": (C.c_int, [vp, vp, vp, i64, vp, i64, vp, vp]),
+    "ppg_shard_set_readtrim": (C.c_int, [vp, vp, vp, i64, vp, i64]),
+    "ppg_shard_readtrim_ready": (C.c_int, [vp, vp, vp]),
+    "ppg_cursor_open_trim": (C.c_int, [vp, vp, C.c_char_p, i32, i32, i64, C.c_int, vp, i32, vp, vp, P(vp)]),
+    "ppg_cursor_selected_trim": (C.c_int, [vp, P(vp)]),
+    "ppg_cursor_trim_result": (C.c_int, [vp, vp]),
     "ppg_shard_select_size": (C.c_int, [vp, vp, i64, P(i64), P(i64)]),
     "ppg_shard_select_records": (C.c_int, [vp, vp, i64, vp, vp, vp, i64, vp, i64, P(i64), P(i64)]),
     "ppg_shard_set_select": (C.c_int, [vp, vp, i64, vp, vp, vp, i64, vp, i64]),
@@ -197,6 +204,23 @@ class PpgReadFilterResult(C.Structure):
 
 
 PPG_FILTER_LENGTH, PPG_FILTER_OTHER, PPG_FILTER_MEAN, PPG_FILTER_LOW, PPG_FILTER_AND_MASK = 1, 2, 4, 8, 0x100
+
+
+class PpgReadTrim(C.Structure):
+    """ppg_read_trim (include/ppgpu.h)."""
+    _fields_ = [("ops", C.c_int64), ("head", C.c_int64), ("tail", C.c_int64), ("qual_base", C.c_int64),
+                ("lead_q", C.c_int64), ("trail_q", C.c_int64), ("win_size", C.c_int64), ("win_q", C.c_int64),
+                ("min_overlap", C.c_int64), ("max_err_milli", C.c_int64), ("min_len", C.c_int64),
+                ("adapter_len", C.c_int64), ("adapter", C.c_uint8 * 64)]
+
+
+class PpgReadTrimResult(C.Structure):
+    """ppg_read_trim_result (include/ppgpu.h)."""
+    _fields_ = [("records", C.c_int64), ("kept", C.c_int64), ("trimmed", C.c_int64), ("cut", C.c_int64 * 5),
+                ("bases", C.c_int64), ("bases_window", C.c_int64), ("bases_kept", C.c_int64)]
+
+
+PPG_TRIM_LEADING, PPG_TRIM_TRAILING, PPG_TRIM_WINDOW, PPG_TRIM_ADAPTER, PPG_TRIM_AND_MASK = 1, 2, 4, 8, 0x100
 
 
 for _name, (_res, _args) in _SIGS.items():

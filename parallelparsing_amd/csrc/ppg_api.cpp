@@ -44,6 +44,10 @@ static bool readfilter_linked() {
     return seq_linked() && ppg_launch_rf_measure && ppg_launch_rf_decide && ppg_launch_rf_totals;
 }
 
+static bool readtrim_linked() {
+    return seq_linked() && ppg_launch_rt_measure && ppg_launch_rt_decide && ppg_launch_rt_totals && ppg_launch_rt_gather;
+}
+
 static bool select_linked() {
     return ppg_launch_sel_count && ppg_launch_sel_scan && ppg_launch_sel_place && ppg_launch_sel_copy;
 }
@@ -791,6 +795,7 @@ int shard_read_filter(ppg_shard *sh, int32_t b0, int32_t b1, const uint32_t *rec
     int64_t total = sh->sq_total;
     if (!laid_out) {
         if (int rc = shard_seq_layout(sh, b0, b1, recs, &total)) return rc;
+        sh->sq_total = total;   // (the trim hook after this one reuses the layout)
         HIPCHK(grow_buf(sh->sq_off, (size_t)tot + 1));
         HIPCHK(grow_buf(sh->sq_len, (size_t)tot + 1));
         HIPCHK(ppg_launch_seq_offsets(s, sh->res.p + b0, sh->info.p + b0, sh->base.p + b0, recs, sh->sp_cbase.p, 0,
@@ -827,6 +832,86 @@ void readfilter_outputs(const ppg_shard *sh, int64_t *chunk_passed, void *result
     }
     if (result) memcpy(result, host, sizeof(ppg_read_filter_result));
     if (chunk_passed && sh->n) memcpy(chunk_passed, host + kRfAcc, 8 * (size_t)sh->n);
+}
+
+// ---- read trimming (ppg_readtrim.hip) ----
+// the rules of include/ppgpu.h "read trimming"; host only
+bool readtrim_ok(const void *trim, PpgReadTrim *out) {
+    if (!trim) return false;
+    ppg_read_trim t;
+    memcpy(&t, trim, sizeof t);
+    if (t.ops & ~(int64_t)0x10F) return false;
+    if (t.head < 0 || t.tail < 0 || t.min_len < 0) return false;
+    if (t.qual_base < 0 || t.qual_base > 255) return false;
+    const int64_t q[3] = {t.lead_q, t.trail_q, t.win_q};
+    for (int i = 0; i < 3; i++)
+        if ((t.ops & (1 << i)) && (q[i] < 0 || q[i] > 256 || t.qual_base + q[i] > 256)) return false;
+    if ((t.ops & 4) && (t.win_size < 1 || t.win_size > 32)) return false;
+    if (t.ops & 8) {
+        if (t.adapter_len < 1 || t.adapter_len > 64) return false;
+        for (int64_t i = 0; i < t.adapter_len; i++)
+            if (t.adapter[i] == '\n') return false;
+        if (t.min_overlap < 1 || t.min_overlap > t.adapter_len) return false;
+        if (t.max_err_milli < 0 || t.max_err_milli > 1000) return false;
+    }
+    if (out) {
+        *out = PpgReadTrim{t.ops, t.head, t.tail, t.qual_base, t.lead_q, t.trail_q, t.win_size, t.win_q, t.min_overlap,
+                           t.max_err_milli, t.min_len, t.adapter_len, {}};
+        for (int i = 0; i < 64; i++) out->adapter[i >> 2] |= (uint32_t)t.adapter[i] << (8 * (i & 3));
+    }
+    return true;
+}
+
+static bool readtrim_bufs_ok(const PpgReadTrim &t, const uint32_t *mask, int64_t rec_cap, const void *rows, int64_t rows_cap) {
+    if (!seqquery_mask_ok(mask, rec_cap) || ((t.ops & 0x100) && !mask)) return false;
+    return rows_cap >= 0 && ((uintptr_t)rows & 7) == 0 && (rows != nullptr || rows_cap == 0);
+}
+
+int shard_read_trim(ppg_shard *sh, int32_t b0, int32_t b1, const uint32_t *recs, int64_t rec0, int64_t tot,
+                    const PpgReadTrim &trm, uint32_t *mask, uint32_t *rows, bool first, bool laid_out) {
+    hipStream_t s = shard_stream(sh);
+    const int nb = b1 - b0;
+    if (!readtrim_linked()) return PPG_UNSUPPORTED;
+    int64_t total = sh->sq_total;
+    if (!laid_out) {
+        if (int rc = shard_seq_layout(sh, b0, b1, recs, &total)) return rc;
+        sh->sq_total = total;
+        HIPCHK(grow_buf(sh->sq_off, (size_t)tot + 1));
+        HIPCHK(grow_buf(sh->sq_len, (size_t)tot + 1));
+        HIPCHK(ppg_launch_seq_offsets(s, sh->res.p + b0, sh->info.p + b0, sh->base.p + b0, recs, sh->sp_cbase.p, 0,
+                                      sh->sq_off.p, sh->sq_len.p, nb));
+    }
+    HIPCHK(grow_buf(sh->rt_rsc, 4 * ((size_t)tot + 1)));
+    HIPCHK(sh->rt_acc.alloc(kRtAcc));
+    HIPCHK(sh->rt_host.alloc(8 * ((size_t)kRtAcc + (size_t)sh->n)));
+    if (first) HIPCHK(hipMemsetAsync(sh->rt_acc.p, 0, 8 * (size_t)kRtAcc, s));
+    if (tot) {   // "none found": all ones for the three minima, 0 for the maximum
+        HIPCHK(hipMemsetAsync(sh->rt_rsc.p, 0xFF, 12 * (size_t)tot, s));
+        HIPCHK(hipMemsetAsync(sh->rt_rsc.p + 3 * (size_t)tot, 0, 4 * (size_t)tot, s));
+    }
+    if (mask && !(trm.ops & 0x100)) {   // as the filter: this batch's words; AND_MASK changes its bits alone
+        const uint64_t w0 = ((uint64_t)rec0 + 31) / 32, w1 = ((uint64_t)rec0 + (uint64_t)tot + 31) / 32;
+        if (w1 > w0) HIPCHK(hipMemsetAsync(mask + w0, 0, 4 * (size_t)(w1 - w0), s));
+    }
+    HIPCHK(ppg_launch_rt_measure(s, sh->out.p, sh->jobs.p + b0, sh->offs.p, sh->oref.p + b0, sh->info.p + b0,
+                                 sh->base.p + b0, recs, sh->sp_cbase.p, sh->sq_off.p, sh->sq_len.p, (uint64_t)total, &trm,
+                                 sh->rt_rsc.p, (uint64_t)tot, nb));
+    int64_t *host = (int64_t *)sh->rt_host.p;
+    HIPCHK(ppg_launch_rt_decide(s, sh->res.p + b0, sh->info.p + b0, sh->base.p + b0, recs, sh->rt_rsc.p, (uint64_t)tot, &trm,
+                                mask, (uint64_t)rec0, rows, sh->rt_acc.p, host + kRtAcc + b0, nb));
+    HIPCHK(ppg_launch_rt_totals(s, sh->rt_acc.p, host));
+    return PPG_OK;
+}
+
+// what the last completed trim left in pinned memory
+void readtrim_outputs(const ppg_shard *sh, int64_t *chunk_kept, void *result) {
+    const int64_t *host = (const int64_t *)sh->rt_host.p;
+    if (!host) {   // a shard without chunks: no batch ran
+        if (result) memset(result, 0, sizeof(ppg_read_trim_result));
+        return;
+    }
+    if (result) memcpy(result, host, sizeof(ppg_read_trim_result));
+    if (chunk_kept && sh->n) memcpy(chunk_kept, host + kRtAcc, 8 * (size_t)sh->n);
 }
 
 // ---- record selection (ppg_seqselect.hip) ----
@@ -987,7 +1072,16 @@ int batch_collect(ppg_shard *sh, int32_t b0, int32_t b1, float &total_ms) {
                                        sh->rf_metrics, b0 == 0, sh->sq_on != 0))
             return rc;
     }
-    // selection of the batch's records, likewise and last: a query or filter hook has filled this
+    // read trim of the batch, likewise, after the filter: with AND_MASK it sees what the query and the
+    // filter have left of this batch's bits (ppg_shard_set_readtrim)
+    if (sh->rt_on) {
+        const int64_t after = sh->total_records + (int64_t)tot;
+        if ((sh->rt_mask && after > sh->rt_rec_cap) || (sh->rt_rows && after > sh->rt_rows_cap)) return PPG_BUF_ERROR;
+        if (int rc = shard_read_trim(sh, b0, b1, sh->recs.p + r0, sh->total_records, (int64_t)tot, sh->rt_trm, sh->rt_mask,
+                                     sh->rt_rows, b0 == 0, sh->sq_on != 0 || sh->rf_on != 0))
+            return rc;
+    }
+    // selection of the batch's records, likewise and last: a query, filter or trim hook has filled this
     // batch's bits of a mask they share (ppg_shard_set_select)
     if (sh->sel_on)
         if (int rc = select_hook(sh, b0, b1, (int64_t)tot)) return rc;
@@ -1041,12 +1135,14 @@ int ppg_shard_run(ppg_shard *sh) {
     sh->sp_written = 0;
     sh->sq_written = 0;
     sh->rf_written = 0;
+    sh->rt_written = 0;
     sh->sel_written = 0;
     sh->last_rc = shard_run(sh);
     sh->keys_written = sh->last_rc == PPG_OK && sh->keys_dev != nullptr;
     sh->sp_written = sh->last_rc == PPG_OK && sh->sp_off != nullptr;
     sh->sq_written = sh->last_rc == PPG_OK && sh->sq_on;
     sh->rf_written = sh->last_rc == PPG_OK && sh->rf_on;
+    sh->rt_written = sh->last_rc == PPG_OK && sh->rt_on;
     sh->sel_written = sh->last_rc == PPG_OK && sh->sel_on;
     return sh->last_rc;
 }
@@ -1418,6 +1514,50 @@ int ppg_shard_readfilter_ready(ppg_shard *sh, int64_t *chunk_passed, void *resul
     return 1;
 }
 
+// ---- read trimming: the read filters entry points' counterparts ----
+int ppg_read_trim_check(const void *trim) { return readtrim_ok(trim, nullptr) ? PPG_OK : PPG_ARG_ERROR; }
+
+int ppg_shard_trim_reads(ppg_shard *sh, const void *trim, uint32_t *dev_keep_mask, int64_t rec_cap, void *dev_trim,
+                         int64_t trim_cap, int64_t *chunk_kept, void *result) {
+    PpgReadTrim trm;
+    if (!sh || !sh->ran || sh->batches.size() != 1 || !readtrim_ok(trim, &trm) ||
+        !readtrim_bufs_ok(trm, dev_keep_mask, rec_cap, dev_trim, trim_cap))
+        return PPG_ARG_ERROR;
+    if (!readtrim_linked()) return PPG_UNSUPPORTED;
+    if ((dev_keep_mask && sh->total_records > rec_cap) || (dev_trim && sh->total_records > trim_cap)) return PPG_BUF_ERROR;
+    HIPCHK(hipSetDevice(sh->ctx->device));
+    sh->rt_written = 0;   // the pinned outputs are rewritten: an earlier run's hook result is gone
+    if (int rc = shard_read_trim(sh, 0, sh->n, sh->recs.p, 0, sh->total_records, trm, dev_keep_mask, (uint32_t *)dev_trim, true,
+                                 false))
+        return rc;
+    HIPCHK(hipStreamSynchronize(shard_stream(sh)));
+    readtrim_outputs(sh, chunk_kept, result);
+    return PPG_OK;
+}
+
+int ppg_shard_set_readtrim(ppg_shard *sh, const void *trim, uint32_t *dev_keep_mask, int64_t rec_cap, void *dev_trim,
+                           int64_t trim_cap) {
+    if (!sh) return PPG_ARG_ERROR;
+    PpgReadTrim trm = {};
+    if (trim && (!readtrim_ok(trim, &trm) || !readtrim_bufs_ok(trm, dev_keep_mask, rec_cap, dev_trim, trim_cap)))
+        return PPG_ARG_ERROR;
+    sh->rt_on = trim ? 1 : 0;
+    sh->rt_trm = trm;
+    sh->rt_mask = trim ? dev_keep_mask : nullptr;
+    sh->rt_rec_cap = trim ? rec_cap : 0;
+    sh->rt_rows = trim ? (uint32_t *)dev_trim : nullptr;
+    sh->rt_rows_cap = trim ? trim_cap : 0;
+    sh->rt_written = 0;   // completed by the next run, not by an earlier one
+    return PPG_OK;
+}
+
+int ppg_shard_readtrim_ready(ppg_shard *sh, int64_t *chunk_kept, void *result) {
+    if (!sh) return PPG_ARG_ERROR;
+    if (!sh->rt_written) return 0;
+    readtrim_outputs(sh, chunk_kept, result);
+    return 1;
+}
+
 // ---- record selection: the sequence queries entry points' counterparts ----
 static bool select_bufs_ok(const int64_t *recno, const int64_t *sel_off, const uint32_t *desc, int64_t sel_cap,
                            const uint8_t *bytes, int64_t byte_cap) {
@@ -1766,6 +1906,74 @@ int ppgx_readfilter_times(ppg_shard *sh, const void *filter, int with_mask, int 
     (void)hipEventDestroy(e0);
     (void)hipEventDestroy(e1);
     sh->rf_written = 0;   // the pinned outputs no longer belong to a run
+    return rc;
+}
+
+// Measurement hook of tools/readtrim_probe.py (not part of the ABI), as ppgx_readfilter_times: the median
+// of reps launches after one warm-up each, into ms[0..3]: the layout, the measure kernel without the
+// ADAPTER bit and with the trim's ops as they are (both with the initialisation of the scratch; equal ops
+// when the trim has no adapter), and the decide kernel (with the clearing of its mask words, writing the
+// rows) + the totals' store.  with_mask: the decide kernel writes a scratch mask.
+int ppgx_readtrim_times(ppg_shard *sh, const void *trim, int with_mask, int reps, float *ms) {
+    PpgReadTrim trm;
+    if (!sh || !sh->ran || sh->batches.size() != 1 || !ms || reps < 1 || !readtrim_ok(trim, &trm) || (trm.ops & 0x100))
+        return PPG_ARG_ERROR;
+    HIPCHK(hipSetDevice(sh->ctx->device));
+    hipStream_t s = shard_stream(sh);
+    const int64_t tot = sh->total_records;
+    DevBuf<uint32_t> words, rows;
+    if (with_mask) HIPCHK(words.alloc((size_t)tot / 32 + 1));
+    HIPCHK(rows.alloc(2 * (size_t)tot + 2));
+    // one whole trim first: it sizes the scratch buffers and leaves the layout in place
+    int rc = shard_read_trim(sh, 0, sh->n, sh->recs.p, 0, tot, trm, words.p, rows.p, true, false);
+    if (rc != PPG_OK) return rc;
+    HIPCHK(hipStreamSynchronize(s));
+    const uint64_t total = *(volatile uint64_t *)sh->sp_htot.p;
+    int64_t *host = (int64_t *)sh->rt_host.p;
+    PpgReadTrim plain = trm;
+    plain.ops &= ~(int64_t)8;
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    HIPCHK(hipEventCreate(&e0));
+    HIPCHK(hipEventCreate(&e1));
+    for (int what = 0; what < 4 && rc == PPG_OK; what++) {
+        std::vector<float> t;
+        for (int r = 0; r <= reps && rc == PPG_OK; r++) {
+            hipError_t e = hipEventRecord(e0, s);
+            if (e == hipSuccess && what == 0) {
+                e = ppg_launch_seq_totals(s, sh->res.p, sh->info.p, sh->base.p, sh->recs.p, sh->sp_ctot.p, sh->n);
+                if (e == hipSuccess) e = ppg_launch_seq_scan(s, sh->sp_ctot.p, sh->sp_cbase.p, (uint64_t *)sh->sp_htot.p, sh->n);
+                if (e == hipSuccess)
+                    e = ppg_launch_seq_offsets(s, sh->res.p, sh->info.p, sh->base.p, sh->recs.p, sh->sp_cbase.p, 0,
+                                               sh->sq_off.p, sh->sq_len.p, sh->n);
+            } else if (e == hipSuccess && what < 3) {
+                if (tot) e = hipMemsetAsync(sh->rt_rsc.p, 0xFF, 12 * (size_t)tot, s);
+                if (e == hipSuccess && tot) e = hipMemsetAsync(sh->rt_rsc.p + 3 * (size_t)tot, 0, 4 * (size_t)tot, s);
+                if (e == hipSuccess)
+                    e = ppg_launch_rt_measure(s, sh->out.p, sh->jobs.p, sh->offs.p, sh->oref.p, sh->info.p, sh->base.p,
+                                              sh->recs.p, sh->sp_cbase.p, sh->sq_off.p, sh->sq_len.p, total,
+                                              what == 1 ? &plain : &trm, sh->rt_rsc.p, (uint64_t)tot, sh->n);
+            } else if (e == hipSuccess) {
+                if (words.p) e = hipMemsetAsync(words.p, 0, 4 * (size_t)((tot + 31) / 32), s);
+                if (e == hipSuccess)
+                    e = ppg_launch_rt_decide(s, sh->res.p, sh->info.p, sh->base.p, sh->recs.p, sh->rt_rsc.p, (uint64_t)tot, &trm,
+                                             words.p, 0, rows.p, sh->rt_acc.p, host + kRtAcc, sh->n);
+                if (e == hipSuccess) e = ppg_launch_rt_totals(s, sh->rt_acc.p, host);
+            }
+            if (e == hipSuccess) e = hipEventRecord(e1, s);
+            if (e == hipSuccess) e = hipEventSynchronize(e1);
+            float v = 0;
+            if (e == hipSuccess) e = hipEventElapsedTime(&v, e0, e1);
+            if (e != hipSuccess) rc = PPG_DEVICE_ERROR;
+            if (r) t.push_back(v);   // (r = 0 warms up)
+        }
+        if (rc == PPG_OK) {
+            std::sort(t.begin(), t.end());
+            ms[what] = t[t.size() / 2];
+        }
+    }
+    (void)hipEventDestroy(e0);
+    (void)hipEventDestroy(e1);
+    sh->rt_written = 0;   // the pinned outputs no longer belong to a run
     return rc;
 }
 

@@ -69,6 +69,10 @@ struct Slot {
     DevBuf<int64_t> dsel_recno, dsel_off;
     DevBuf<uint8_t> dsel_bytes;
     PinnedBuf hsel_recno, hsel_off, hsel_desc, hsel_bytes;
+    // ... with a trim (ppg_cursor_open_trim): the windows of the batch's records, those of the selected
+    // records in their order, and the latter pinned
+    DevBuf<uint32_t> dtrim, dsel_trim;
+    PinnedBuf hsel_trim;
     int64_t sel_records = 0, sel_nbytes = 0;
     int32_t b0 = 0, b1 = 0;             // chunks [b0, b1) relative to the cursor's first
     int64_t nrec = 0;
@@ -114,6 +118,8 @@ struct ppg_cursor {
     int32_t pat_m = 0;
     bool filter = false;                // ... and pass flt (ppg_cursor_open_filter): the selection is "hit and pass"
     PpgReadFilter flt = {};
+    bool trim = false;                  // ... and are min_len long after trimming by trm (ppg_cursor_open_trim): "hit, pass and keep"
+    PpgReadTrim trm = {};
     const Slot *cur = nullptr;          // the batch handed out last (the packed / selected accessors read it)
     int64_t cur_base = 0;               // ... and its record_base
     int64_t pk_rec = 0, pk_bases = 0;   // packed slots: records / padded bases they are sized for at open
@@ -192,12 +198,13 @@ struct ppg_cursor {
         // a select slot: the selection buffers for the whole batch's text on the device, the scratch of the
         // query and the selection (~40 B per record); pinned, what batches select: unknown before the first
         // count pass unless every record is selected (no pattern), which is the whole text
-        const bool select_all = select && pat_m == 0 && !filter;
-        // (pin_select: the text, and 32 B of descriptor, record number and offset per record)
-        const double sel_pinned = select_all ? (double)rmax + 32.0 * (double)pk_rec : (double)(256 << 10) + 32.0 * 1024;
+        const bool select_all = select && pat_m == 0 && !filter && !trim;
+        // (pin_select: the text, and 32 B of descriptor, record number and offset per record; a trim's
+        // 8 B of window per selected record are within the margin of the second form)
+        const double sel_pinned = select_all ? (double)rmax + 32.0 * (double)pk_rec : (double)(256 << 10) + 40.0 * 1024;
         const double host_slot = (double)cmax + (packed ? pk_bytes : select ? sel_pinned : (double)rmax * 1.125);
         const double dev_slot = (double)cmax + (packed   ? (double)rmax * 1.4 + pk_bytes
-                                                : select ? (double)rmax * 2.4 + 72.0 * (double)pk_rec
+                                                : select ? (double)rmax * 2.4 + (trim ? 104.0 : 72.0) * (double)pk_rec
                                                          : (double)rmax * (pack == 1 ? 2.4 : 1.4));
         size_t dfree = 0, dtotal = 0;
         const double havail = host_mem_available();
@@ -255,6 +262,10 @@ struct ppg_cursor {
         HIPCHK(s.dsel_recno.alloc((size_t)nrec));
         HIPCHK(s.dsel_off.alloc((size_t)nrec + 1));
         HIPCHK(s.dsel_desc.alloc(4 * (size_t)nrec + 4));
+        if (trim) {   // 8 B of window per record, and per selected record
+            HIPCHK(s.dtrim.alloc(2 * (size_t)nrec + 2));
+            HIPCHK(s.dsel_trim.alloc(2 * (size_t)nrec + 2));
+        }
         return PPG_OK;
     }
 
@@ -264,6 +275,7 @@ struct ppg_cursor {
         HIPCHK(s.hsel_off.alloc(8 * ((size_t)nrec + 1)));
         HIPCHK(s.hsel_desc.alloc(16 * (size_t)nrec));
         HIPCHK(s.hsel_bytes.alloc((size_t)nbytes));
+        if (trim) HIPCHK(s.hsel_trim.alloc(8 * (size_t)nrec + 8));
         return PPG_OK;
     }
 
@@ -349,6 +361,10 @@ struct ppg_cursor {
             if (filter)
                 if (int rc = shard_read_filter(&s.sh, 0, m, s.sh.recs.p, 0, s.nrec, flt, s.dsel_mask.p, nullptr, true, true))
                     return rc;
+            // the trim clears the bits of the records that end up shorter than min_len, and leaves every record's window
+            if (trim)
+                if (int rc = shard_read_trim(&s.sh, 0, m, s.sh.recs.p, 0, s.nrec, trm, s.dsel_mask.p, s.dtrim.p, true, true))
+                    return rc;
             if (int rc = shard_select_sizes(&s.sh, 0, m, s.sh.recs.p, s.dsel_mask.p, 0, &s.sel_records, &s.sel_nbytes))
                 return rc;
             if ((size_t)s.sel_nbytes + 16 > s.dsel_bytes.n) return PPG_BUF_ERROR;   // a selection is part of the text: never
@@ -357,6 +373,8 @@ struct ppg_cursor {
             if (int rc = shard_select_move(&s.sh, 0, m, s.sh.recs.p, s.dsel_mask.p, 0, 0, 0, s.sel_records, s.sel_nbytes,
                                            s.dsel_recno.p, s.dsel_off.p, s.dsel_desc.p, s.dsel_bytes.p))
                 return rc;
+            if (trim)   // the selected records' windows, in the selection's order (recno counts from the batch's first record)
+                HIPCHK(ppg_launch_rt_gather(st, s.dtrim.p, s.dsel_recno.p, 0, (uint64_t)s.sel_records, s.dsel_trim.p));
             stage_wait(i, kHost);
             const double th = ms();
             const size_t nr = (size_t)s.sel_records;
@@ -364,6 +382,7 @@ struct ppg_cursor {
             if (nr) {
                 HIPCHK(hipMemcpyAsync(s.hsel_recno.p, s.dsel_recno.p, 8 * nr, hipMemcpyDeviceToHost, st));
                 HIPCHK(hipMemcpyAsync(s.hsel_desc.p, s.dsel_desc.p, 16 * nr, hipMemcpyDeviceToHost, st));
+                if (trim) HIPCHK(hipMemcpyAsync(s.hsel_trim.p, s.dsel_trim.p, 8 * nr, hipMemcpyDeviceToHost, st));
             }
             if (s.sel_nbytes)
                 HIPCHK(hipMemcpyAsync(s.hsel_bytes.p, s.dsel_bytes.p, (size_t)s.sel_nbytes, hipMemcpyDeviceToHost, st));
@@ -437,7 +456,7 @@ extern "C" {
 
 static int cursor_open(ppg_ctx *ctx, const ppg_index *ix, const char *gz_path, int32_t first, int32_t n,
                        int64_t batch_bytes, int threads, bool packed, bool quality, const PpgSeqPattern *pat,
-                       int32_t pat_m, const void *filter, ppg_cursor **out) {
+                       int32_t pat_m, const void *filter, const PpgReadTrim *trim, ppg_cursor **out) {
     if (!ctx || !ix || !gz_path || !out || first < 0 || n < 0 || (size_t)first + (size_t)n + 1 > ix->pts.size())
         return PPG_ARG_ERROR;
     if (int v = ppg_index_validate(ix, first, n)) return v;
@@ -460,6 +479,11 @@ static int cursor_open(ppg_ctx *ctx, const ppg_index *ix, const char *gz_path, i
         c->filter = true;
         memcpy(&c->flt, filter, sizeof c->flt);
         c->flt.criteria |= 0x100;
+    }
+    if (trim) {   // (likewise)
+        c->trim = true;
+        c->trm = *trim;
+        c->trm.ops |= 0x100;
     }
     if (const char *e = getenv("PPG_CURSOR_SLOTS")) c->nslots = std::min(kMaxSlots, std::max(2, atoi(e)));
     if (const char *e = getenv("PPG_CURSOR_PACK")) c->pack = std::min(2, std::max(0, atoi(e)));
@@ -502,13 +526,13 @@ static int cursor_open(ppg_ctx *ctx, const ppg_index *ix, const char *gz_path, i
 
 int ppg_cursor_open(ppg_ctx *ctx, const ppg_index *ix, const char *gz_path, int32_t first, int32_t n,
                     int64_t batch_bytes, int threads, ppg_cursor **out) {
-    return cursor_open(ctx, ix, gz_path, first, n, batch_bytes, threads, false, false, nullptr, 0, nullptr, out);
+    return cursor_open(ctx, ix, gz_path, first, n, batch_bytes, threads, false, false, nullptr, 0, nullptr, nullptr, out);
 }
 
 int ppg_cursor_open_packed(ppg_ctx *ctx, const ppg_index *ix, const char *gz_path, int32_t first, int32_t n,
                            int64_t batch_bytes, int threads, int32_t planes, ppg_cursor **out) {
     if (planes & ~1) return PPG_ARG_ERROR;
-    return cursor_open(ctx, ix, gz_path, first, n, batch_bytes, threads, true, (planes & 1) != 0, nullptr, 0, nullptr, out);
+    return cursor_open(ctx, ix, gz_path, first, n, batch_bytes, threads, true, (planes & 1) != 0, nullptr, 0, nullptr, nullptr, out);
 }
 
 int ppg_cursor_packed(const ppg_cursor *c, uint32_t **bases, uint32_t **mask, uint8_t **qual, uint32_t **seq_len,
@@ -536,7 +560,7 @@ int ppg_cursor_open_select(ppg_ctx *ctx, const ppg_index *ix, const char *gz_pat
                            ppg_cursor **out) {
     PpgSeqPattern pat;
     if (!seqquery_pattern(pattern, pattern_len, &pat)) return PPG_ARG_ERROR;
-    return cursor_open(ctx, ix, gz_path, first, n, batch_bytes, threads, false, false, &pat, pattern_len, nullptr, out);
+    return cursor_open(ctx, ix, gz_path, first, n, batch_bytes, threads, false, false, &pat, pattern_len, nullptr, nullptr, out);
 }
 
 int ppg_cursor_open_filter(ppg_ctx *ctx, const ppg_index *ix, const char *gz_path, int32_t first, int32_t n,
@@ -545,12 +569,36 @@ int ppg_cursor_open_filter(ppg_ctx *ctx, const ppg_index *ix, const char *gz_pat
     PpgSeqPattern pat;
     if (!seqquery_pattern(pattern, pattern_len, &pat) || (filter && ppg_read_filter_check(filter) != PPG_OK))
         return PPG_ARG_ERROR;
-    return cursor_open(ctx, ix, gz_path, first, n, batch_bytes, threads, false, false, &pat, pattern_len, filter, out);
+    return cursor_open(ctx, ix, gz_path, first, n, batch_bytes, threads, false, false, &pat, pattern_len, filter, nullptr, out);
 }
 
 int ppg_cursor_filter_result(const ppg_cursor *c, void *result) {
     if (!c || !c->filter || !c->cur || !result) return PPG_ARG_ERROR;
     readfilter_outputs(&c->cur->sh, nullptr, result);
+    return PPG_OK;
+}
+
+int ppg_cursor_open_trim(ppg_ctx *ctx, const ppg_index *ix, const char *gz_path, int32_t first, int32_t n,
+                         int64_t batch_bytes, int threads, const uint8_t *pattern, int32_t pattern_len,
+                         const void *filter, const void *trim, ppg_cursor **out) {
+    PpgSeqPattern pat;
+    PpgReadTrim trm;
+    if (!seqquery_pattern(pattern, pattern_len, &pat) || (filter && ppg_read_filter_check(filter) != PPG_OK) ||
+        (trim && !readtrim_ok(trim, &trm)))
+        return PPG_ARG_ERROR;
+    return cursor_open(ctx, ix, gz_path, first, n, batch_bytes, threads, false, false, &pat, pattern_len, filter,
+                       trim ? &trm : nullptr, out);
+}
+
+int ppg_cursor_selected_trim(const ppg_cursor *c, uint32_t **trim) {
+    if (!c || !c->trim || !c->cur || !trim) return PPG_ARG_ERROR;
+    *trim = (uint32_t *)c->cur->hsel_trim.p;
+    return PPG_OK;
+}
+
+int ppg_cursor_trim_result(const ppg_cursor *c, void *result) {
+    if (!c || !c->trim || !c->cur || !result) return PPG_ARG_ERROR;
+    readtrim_outputs(&c->cur->sh, nullptr, result);
     return PPG_OK;
 }
 

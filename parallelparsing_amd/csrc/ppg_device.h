@@ -110,6 +110,17 @@ constexpr int kRfAcc = 265;
 // ppg_rf_measure's Quality histogram: one LDS add per run of equal bytes of a lane, or one per byte
 constexpr int kRfHistRuns = 0, kRfHistBytes = 1;
 
+// a ppg_read_trim (include/ppgpu.h "read trimming") as the trim kernels' argument; the adapter's bytes as
+// little-endian dwords
+struct PpgReadTrim {
+    int64_t ops, head, tail, qual_base, lead_q, trail_q, win_size, win_q, min_overlap, max_err_milli, min_len,
+        adapter_len;
+    uint32_t adapter[16];
+};
+// the read trim's accumulators: the int64 fields of a ppg_read_trim_result in order (records, kept, trimmed,
+// cut[5], bases, bases_window, bases_kept)
+constexpr int kRtAcc = 11;
+
 // ppg_sel_copy: the destination bytes one workgroup writes (256 threads x 4 words of 16 B); ppg_sel_place
 // records, per multiple of it inside a batch's destination range, the selected record that holds that byte
 constexpr uint32_t kSelSpan = 16384;

@@ -228,6 +228,18 @@ struct ppg_shard {
     DevBuf<uint64_t> rf_rsc;             // scratch: other | low << 32 and qsum of one batch's records
     DevBuf<uint64_t> rf_acc;             // kRfAcc accumulators of the run so far
     PinnedBuf rf_host;                   // a ppg_read_filter_result, then passes per chunk: stored by the kernels
+    // ppg_shard_set_readtrim: every batch's records are also trimmed (ppg_readtrim.hip); keep bits and
+    // (start, len) rows at the shard record number, totals carried in rt_acc
+    int rt_on = 0;
+    PpgReadTrim rt_trm = {};
+    uint32_t *rt_mask = nullptr;
+    int64_t rt_rec_cap = 0;
+    uint32_t *rt_rows = nullptr;
+    int64_t rt_rows_cap = 0;
+    int rt_written = 0;                  // the last successful run completed the trim (set by shard_run)
+    DevBuf<uint32_t> rt_rsc;             // scratch: four planes (lead, win, adapt, trail) of one batch's records
+    DevBuf<uint64_t> rt_acc;             // kRtAcc accumulators of the run so far
+    PinnedBuf rt_host;                   // a ppg_read_trim_result, then keeps per chunk: stored by the kernels
     // ppg_shard_set_select: every batch's selected records are also appended to these buffers
     // (ppg_seqselect.hip), output records and bytes continuing from the batches before
     int sel_on = 0;
@@ -308,6 +320,15 @@ bool seqquery_pattern(const uint8_t *pattern, int32_t m, PpgSeqPattern *pat);
 int shard_read_filter(ppg_shard *sh, int32_t b0, int32_t b1, const uint32_t *recs, int64_t rec0, int64_t tot,
                       const PpgReadFilter &flt, uint32_t *mask, uint8_t *metrics, bool first, bool laid_out);
 void readfilter_outputs(const ppg_shard *sh, int64_t *chunk_passed, void *result);
+// read trim of chunks [b0, b1) of one resident batch, with the arguments of shard_read_filter; mask and
+// rows may be null (rows: row 0 of the plane, two words per record).  laid_out: a shard_seq_query or a
+// shard_read_filter of the same chunks has just run.  The totals so far and the chunks' keeps are in
+// rt_host once the stream has drained.  readtrim_ok: the rules of ppg_read_trim_check, the struct as the
+// kernels' argument.
+int shard_read_trim(ppg_shard *sh, int32_t b0, int32_t b1, const uint32_t *recs, int64_t rec0, int64_t tot,
+                    const PpgReadTrim &trm, uint32_t *mask, uint32_t *rows, bool first, bool laid_out);
+void readtrim_outputs(const ppg_shard *sh, int64_t *chunk_kept, void *result);
+bool readtrim_ok(const void *trim, PpgReadTrim *out);
 // record selection of chunks [b0, b1) of one resident batch (recs: the batch's first descriptor; record j
 // of the batch has bit bit0 + j of mask, a null mask selects all).  sizes: the selected records and their
 // bytes (blocks on the shard's stream).  move: after sizes of the same chunks, queues the selection into

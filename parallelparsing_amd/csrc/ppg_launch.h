@@ -105,6 +105,21 @@ PPG_WEAK hipError_t ppg_launch_rf_decide(hipStream_t s, const uint8_t *out, cons
                                          uint8_t *metrics, uint64_t *acc, int64_t *host_chunk_passed, int n);
 PPG_WEAK hipError_t ppg_launch_rf_totals(hipStream_t s, const uint64_t *acc, int64_t *host_result);
 
+// ---- ppg_readtrim.hip ----
+// Weak for the same reason (readtrim_linked, ppg_api.cpp).
+PPG_WEAK hipError_t ppg_launch_rt_measure(hipStream_t s, const uint8_t *out, const PpgInflateJob *jobs,
+                                          const uint8_t *offs, const PpgOffsetRef *oref, const PpgParseInfo *info,
+                                          const uint64_t *base, const uint32_t *recs, const uint64_t *cbase,
+                                          const int64_t *seq_off, const uint32_t *seq_len, uint64_t total,
+                                          const PpgReadTrim *tr, uint32_t *rsc, uint64_t tot, int n);
+PPG_WEAK hipError_t ppg_launch_rt_decide(hipStream_t s, const PpgInflateResult *ires, const PpgParseInfo *info,
+                                         const uint64_t *base, const uint32_t *recs, const uint32_t *rsc, uint64_t tot,
+                                         const PpgReadTrim *tr, uint32_t *words, uint64_t rec0, uint32_t *trim,
+                                         uint64_t *acc, int64_t *host_chunk_kept, int n);
+PPG_WEAK hipError_t ppg_launch_rt_totals(hipStream_t s, const uint64_t *acc, int64_t *host_result);
+PPG_WEAK hipError_t ppg_launch_rt_gather(hipStream_t s, const uint32_t *trim, const int64_t *recno, int64_t rec0,
+                                         uint64_t n, uint32_t *dst);
+
 // ---- ppg_seqselect.hip ----
 // Weak for the same reason (select_linked, ppg_api.cpp).
 PPG_WEAK hipError_t ppg_launch_sel_count(hipStream_t s, const PpgInflateResult *ires, const PpgParseInfo *info,

@@ -29,6 +29,9 @@
 #                               the text cursor -> profiles/seqselect_probe.json + seqselect_probe.log
 #   readfilter[:args]           tools/readfilter_probe.py: read filter kernels against ppg_seq_query, CountPassing
 #                               and Where(filter) against the text cursor -> profiles/readfilter_probe.json + readfilter_probe.log
+#   readtrim[:args]             tools/readtrim_probe.py: read trim kernels against ppg_rf_measure and ppg_seq_query,
+#                               CountTrimmed and Where(trim) against Where(filter) and the text cursor
+#                               -> profiles/readtrim_probe.json + readtrim_probe.log
 set -o pipefail
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT" || exit 1
 tag=$1; shift
@@ -124,6 +127,11 @@ run_step() {
       > $O/readfilter_probe.out 2> $O/readfilter_probe.log || { tail -5 $O/readfilter_probe.log; return 1; }
     cp profiles/readfilter_probe.json $O/
     python3 -c "import json,sys; d=json.load(open(sys.argv[1])); print(json.dumps(d['kernels'])[:2500]); print(d['file']); print({k: (round(v['records_per_s']/1e6,1), v['bytes_to_host']) for k, v in d['from_file'].items()})" $O/readfilter_probe.json ;;
+  readtrim)
+    env ${SELECT_VERBOSE:+PPG_CURSOR_VERBOSE=1} timeout -k 10 500 python3 -u tools/readtrim_probe.py $xa \
+      > $O/readtrim_probe.out 2> $O/readtrim_probe.log || { tail -5 $O/readtrim_probe.log; return 1; }
+    cp profiles/readtrim_probe.json $O/
+    python3 -c "import json,sys; d=json.load(open(sys.argv[1])); print(json.dumps(d['kernels'])[:2500]); print(d['file']); print({k: (round(v['records_per_s']/1e6,1), v['bytes_to_host']) for k, v in d['from_file'].items()})" $O/readtrim_probe.json ;;
   *)
     echo "gpu_run.sh: unknown step $step" >&2; return 2 ;;
   esac
