@@ -32,26 +32,6 @@
 #include "ppg_host.h"
 #include "ppg_launch.h"
 
-static bool seq_linked() {   // (weak references, ppg_launch.h: absent from the host-only sanitizer build)
-    return ppg_launch_seq_totals && ppg_launch_seq_scan && ppg_launch_seq_offsets && ppg_launch_seq_pack;
-}
-
-static bool seqquery_linked() {
-    return seq_linked() && ppg_launch_seq_query && ppg_launch_seq_query_chunks && ppg_launch_seq_query_totals;
-}
-
-static bool readfilter_linked() {
-    return seq_linked() && ppg_launch_rf_measure && ppg_launch_rf_decide && ppg_launch_rf_totals;
-}
-
-static bool readtrim_linked() {
-    return seq_linked() && ppg_launch_rt_measure && ppg_launch_rt_decide && ppg_launch_rt_totals && ppg_launch_rt_gather;
-}
-
-static bool select_linked() {
-    return ppg_launch_sel_count && ppg_launch_sel_scan && ppg_launch_sel_place && ppg_launch_sel_copy;
-}
-
 namespace {
 
 // Byte source read in FileStream.Read(input, 0, CHUNK) steps (Core.cs:41).
@@ -649,329 +629,6 @@ void shard_reset(ppg_shard *sh) {
     sh->ran = 0;
 }
 
-// ---- packed reads (ppg_seqpack.hip) ----
-int shard_seq_reserve(ppg_shard *sh, int64_t nchunks) {
-    HIPCHK(sh->sp_ctot.alloc((size_t)nchunks + 1));
-    HIPCHK(sh->sp_cbase.alloc((size_t)nchunks + 1));
-    HIPCHK(sh->sp_htot.alloc(8));
-    return PPG_OK;
-}
-
-int shard_seq_layout(ppg_shard *sh, int32_t b0, int32_t b1, const uint32_t *recs, int64_t *total) {
-    hipStream_t s = shard_stream(sh);
-    const int nb = b1 - b0;
-    if (!seq_linked()) return PPG_UNSUPPORTED;
-    if (int rc = shard_seq_reserve(sh, std::max<int64_t>(nb, sh->n))) return rc;   // once: every batch fits
-    HIPCHK(ppg_launch_seq_totals(s, sh->res.p + b0, sh->info.p + b0, sh->base.p + b0, recs, sh->sp_ctot.p, nb));
-    HIPCHK(ppg_launch_seq_scan(s, sh->sp_ctot.p, sh->sp_cbase.p, (uint64_t *)sh->sp_htot.p, nb));
-    HIPCHK(hipStreamSynchronize(s));
-    *total = (int64_t)*(volatile uint64_t *)sh->sp_htot.p;
-    return PPG_OK;
-}
-
-int shard_seq_pack(ppg_shard *sh, int32_t b0, int32_t b1, const uint32_t *recs, int64_t carry, int64_t total,
-                   int64_t *seq_off, uint32_t *seq_len, uint32_t *bases, uint32_t *mask, uint8_t *qual) {
-    hipStream_t s = shard_stream(sh);
-    const int nb = b1 - b0;
-    if (!seq_linked()) return PPG_UNSUPPORTED;
-    HIPCHK(ppg_launch_seq_offsets(s, sh->res.p + b0, sh->info.p + b0, sh->base.p + b0, recs, sh->sp_cbase.p, carry,
-                                  seq_off, seq_len, nb));
-    HIPCHK(ppg_launch_seq_pack(s, sh->out.p, sh->jobs.p + b0, sh->res.p + b0, sh->offs.p, sh->oref.p + b0,
-                               sh->info.p + b0, sh->base.p + b0, recs, sh->sp_cbase.p, seq_off, seq_len, carry,
-                               (uint64_t)total, bases, mask, qual, nb));
-    return PPG_OK;
-}
-
-// batch_collect's hook: the batch's tot records go to shard record numbers [total_records, + tot),
-// their bases continue from the batches before.  Nothing is written when a cap would be exceeded.
-static int seq_hook(ppg_shard *sh, int32_t b0, int32_t b1, int64_t tot) {
-    if (sh->total_records == 0) sh->sp_total = 0;   // the run's first batch
-    const uint32_t *recs = sh->recs.p + 4 * (uint64_t)sh->total_records;
-    int64_t total = 0;
-    if (int rc = shard_seq_layout(sh, b0, b1, recs, &total)) return rc;
-    if (sh->total_records + tot > sh->sp_rec_cap || sh->sp_total + total > sh->sp_base_cap) return PPG_BUF_ERROR;
-    if (int rc = shard_seq_pack(sh, b0, b1, recs, sh->sp_total, total, sh->sp_off + sh->total_records,
-                                sh->sp_len + sh->total_records, sh->sp_bases, sh->sp_mask, sh->sp_qual))
-        return rc;
-    sh->sp_total += total;
-    return PPG_OK;
-}
-
-// ---- sequence queries (ppg_seqquery.hip) ----
-int shard_seq_query(ppg_shard *sh, int32_t b0, int32_t b1, const uint32_t *recs, int64_t rec0, int64_t tot,
-                    const PpgSeqPattern &pat, int32_t m, uint32_t *mask, bool first) {
-    hipStream_t s = shard_stream(sh);
-    const int nb = b1 - b0;
-    if (!seqquery_linked()) return PPG_UNSUPPORTED;
-    int64_t total = 0;
-    if (int rc = shard_seq_layout(sh, b0, b1, recs, &total)) return rc;
-    sh->sq_total = total;
-    HIPCHK(grow_buf(sh->sq_off, (size_t)tot + 1));
-    HIPCHK(grow_buf(sh->sq_len, (size_t)tot + 1));
-    HIPCHK(sh->sq_acc.alloc(8));
-    HIPCHK(sh->sq_host.alloc(8 * (8 + (size_t)sh->n)));
-    if (first) HIPCHK(hipMemsetAsync(sh->sq_acc.p, 0, 64, s));
-    // the hit bits: the caller's mask at the shard record number, else (a pattern, no mask) scratch
-    // at the batch's record number; a census alone with no mask needs none
-    uint32_t *words = mask;
-    uint64_t bit0 = (uint64_t)rec0;
-    if (!mask && m > 0) {
-        HIPCHK(grow_buf(sh->sq_bits, (size_t)tot / 32 + 1));
-        words = sh->sq_bits.p;
-        bit0 = 0;
-    }
-    if (words) {
-        // the words whose first bit is this batch's or later; the word a batch shares with the one
-        // before it was cleared by that batch
-        const uint64_t w0 = (bit0 + 31) / 32, w1 = (bit0 + (uint64_t)tot + 31) / 32;
-        if (w1 > w0) HIPCHK(hipMemsetAsync(words + w0, 0, 4 * (size_t)(w1 - w0), s));
-    }
-    HIPCHK(ppg_launch_seq_offsets(s, sh->res.p + b0, sh->info.p + b0, sh->base.p + b0, recs, sh->sp_cbase.p, 0,
-                                  sh->sq_off.p, sh->sq_len.p, nb));
-    HIPCHK(ppg_launch_seq_query(s, sh->out.p, sh->jobs.p + b0, sh->offs.p, sh->oref.p + b0, sh->info.p + b0,
-                                sh->base.p + b0, recs, sh->sp_cbase.p, sh->sq_off.p, sh->sq_len.p, (uint64_t)total, &pat,
-                                m, words, bit0, sh->sq_acc.p, nb));
-    int64_t *host = (int64_t *)sh->sq_host.p;
-    HIPCHK(ppg_launch_seq_query_chunks(s, sh->res.p + b0, sh->info.p + b0, sh->base.p + b0, m, words, bit0,
-                                       sh->sq_acc.p, host + 8 + b0, nb));
-    HIPCHK(ppg_launch_seq_query_totals(s, sh->sq_acc.p, host));
-    return PPG_OK;
-}
-
-// what the last completed query left in pinned memory
-static void seqquery_outputs(const ppg_shard *sh, int64_t *chunk_hits, void *result) {
-    const int64_t *host = (const int64_t *)sh->sq_host.p;
-    if (!host) {   // a shard without chunks: no batch ran
-        if (result) memset(result, 0, sizeof(ppg_seq_query_result));
-        return;
-    }
-    if (result) memcpy(result, host, sizeof(ppg_seq_query_result));
-    if (chunk_hits && sh->n) memcpy(chunk_hits, host + 8, 8 * (size_t)sh->n);
-}
-
-// m bytes of pattern (NULL: m = 0) as the kernel's argument; false for a length outside [0, 64] or a '\n'
-bool seqquery_pattern(const uint8_t *pattern, int32_t m, PpgSeqPattern *pat) {
-    if (m < 0 || m > 64 || (m > 0 && !pattern)) return false;
-    memset(pat, 0, sizeof *pat);
-    for (int32_t i = 0; i < m; i++) {
-        if (pattern[i] == '\n') return false;
-        pat->w[i >> 3] |= (uint64_t)pattern[i] << (8 * (i & 7));
-    }
-    return true;
-}
-
-static bool seqquery_mask_ok(const uint32_t *mask, int64_t rec_cap) {
-    return rec_cap >= 0 && rec_cap % 32 == 0 && ((uintptr_t)mask & 3) == 0 && (mask != nullptr || rec_cap == 0);
-}
-
-// ---- read filters (ppg_readfilter.hip) ----
-// the rules of include/ppgpu.h "read filters"; host only
-static bool readfilter_ok(const void *filter, PpgReadFilter *out) {
-    if (!filter) return false;
-    PpgReadFilter f;
-    memcpy(&f, filter, sizeof f);
-    if (f.criteria & ~(int64_t)0x10F) return false;
-    if (f.min_len < 0 || f.max_len < -1 || (f.max_len >= 0 && f.max_len < f.min_len)) return false;
-    if ((f.criteria & 2) && f.max_other < 0) return false;
-    if (f.qual_base < 0 || f.qual_base > 255) return false;
-    if (f.low_q < 0 || f.low_q > 256 || f.qual_base + f.low_q > 256) return false;
-    if (f.max_low_milli < 0 || f.max_low_milli > 1000) return false;
-    if (f.min_mean_milli > 255000 || f.min_mean_milli < -255000) return false;
-    if (out) *out = f;
-    return true;
-}
-
-static bool readfilter_bufs_ok(const PpgReadFilter &f, const uint32_t *mask, int64_t rec_cap, const uint8_t *metrics,
-                               int64_t metrics_cap) {
-    if (!seqquery_mask_ok(mask, rec_cap) || ((f.criteria & 0x100) && !mask)) return false;
-    return metrics_cap >= 0 && ((uintptr_t)metrics & 7) == 0 && (metrics != nullptr || metrics_cap == 0);
-}
-
-int shard_read_filter(ppg_shard *sh, int32_t b0, int32_t b1, const uint32_t *recs, int64_t rec0, int64_t tot,
-                      const PpgReadFilter &flt, uint32_t *mask, uint8_t *metrics, bool first, bool laid_out) {
-    hipStream_t s = shard_stream(sh);
-    const int nb = b1 - b0;
-    if (!readfilter_linked()) return PPG_UNSUPPORTED;
-    int64_t total = sh->sq_total;
-    if (!laid_out) {
-        if (int rc = shard_seq_layout(sh, b0, b1, recs, &total)) return rc;
-        sh->sq_total = total;   // (the trim hook after this one reuses the layout)
-        HIPCHK(grow_buf(sh->sq_off, (size_t)tot + 1));
-        HIPCHK(grow_buf(sh->sq_len, (size_t)tot + 1));
-        HIPCHK(ppg_launch_seq_offsets(s, sh->res.p + b0, sh->info.p + b0, sh->base.p + b0, recs, sh->sp_cbase.p, 0,
-                                      sh->sq_off.p, sh->sq_len.p, nb));
-    }
-    HIPCHK(grow_buf(sh->rf_rsc, 2 * ((size_t)tot + 1)));
-    HIPCHK(sh->rf_acc.alloc(kRfAcc));
-    HIPCHK(sh->rf_host.alloc(8 * ((size_t)kRfAcc + (size_t)sh->n)));
-    if (first) HIPCHK(hipMemsetAsync(sh->rf_acc.p, 0, 8 * (size_t)kRfAcc, s));
-    if (tot) HIPCHK(hipMemsetAsync(sh->rf_rsc.p, 0, 16 * (size_t)tot, s));
-    if (mask && !(flt.criteria & 0x100)) {
-        // as the query: the words whose first bit is this batch's or later; the word a batch shares with
-        // the one before it was cleared by that batch.  (AND_MASK changes this batch's bits alone.)
-        const uint64_t w0 = ((uint64_t)rec0 + 31) / 32, w1 = ((uint64_t)rec0 + (uint64_t)tot + 31) / 32;
-        if (w1 > w0) HIPCHK(hipMemsetAsync(mask + w0, 0, 4 * (size_t)(w1 - w0), s));
-    }
-    HIPCHK(ppg_launch_rf_measure(s, sh->out.p, sh->jobs.p + b0, sh->offs.p, sh->oref.p + b0, sh->info.p + b0,
-                                 sh->base.p + b0, recs, sh->sp_cbase.p, sh->sq_off.p, sh->sq_len.p, (uint64_t)total,
-                                 (uint32_t)(flt.qual_base + flt.low_q), sh->rf_rsc.p, sh->rf_acc.p, nb, sh->rf_hist));
-    int64_t *host = (int64_t *)sh->rf_host.p;
-    HIPCHK(ppg_launch_rf_decide(s, sh->out.p, sh->jobs.p + b0, sh->res.p + b0, sh->offs.p, sh->oref.p + b0, sh->info.p + b0,
-                                sh->base.p + b0, recs, sh->rf_rsc.p, &flt, mask, (uint64_t)rec0, metrics, sh->rf_acc.p,
-                                host + kRfAcc + b0, nb));
-    HIPCHK(ppg_launch_rf_totals(s, sh->rf_acc.p, host));
-    return PPG_OK;
-}
-
-// what the last completed filter left in pinned memory
-void readfilter_outputs(const ppg_shard *sh, int64_t *chunk_passed, void *result) {
-    const int64_t *host = (const int64_t *)sh->rf_host.p;
-    if (!host) {   // a shard without chunks: no batch ran
-        if (result) memset(result, 0, sizeof(ppg_read_filter_result));
-        return;
-    }
-    if (result) memcpy(result, host, sizeof(ppg_read_filter_result));
-    if (chunk_passed && sh->n) memcpy(chunk_passed, host + kRfAcc, 8 * (size_t)sh->n);
-}
-
-// ---- read trimming (ppg_readtrim.hip) ----
-// the rules of include/ppgpu.h "read trimming"; host only
-bool readtrim_ok(const void *trim, PpgReadTrim *out) {
-    if (!trim) return false;
-    ppg_read_trim t;
-    memcpy(&t, trim, sizeof t);
-    if (t.ops & ~(int64_t)0x10F) return false;
-    if (t.head < 0 || t.tail < 0 || t.min_len < 0) return false;
-    if (t.qual_base < 0 || t.qual_base > 255) return false;
-    const int64_t q[3] = {t.lead_q, t.trail_q, t.win_q};
-    for (int i = 0; i < 3; i++)
-        if ((t.ops & (1 << i)) && (q[i] < 0 || q[i] > 256 || t.qual_base + q[i] > 256)) return false;
-    if ((t.ops & 4) && (t.win_size < 1 || t.win_size > 32)) return false;
-    if (t.ops & 8) {
-        if (t.adapter_len < 1 || t.adapter_len > 64) return false;
-        for (int64_t i = 0; i < t.adapter_len; i++)
-            if (t.adapter[i] == '\n') return false;
-        if (t.min_overlap < 1 || t.min_overlap > t.adapter_len) return false;
-        if (t.max_err_milli < 0 || t.max_err_milli > 1000) return false;
-    }
-    if (out) {
-        *out = PpgReadTrim{t.ops, t.head, t.tail, t.qual_base, t.lead_q, t.trail_q, t.win_size, t.win_q, t.min_overlap,
-                           t.max_err_milli, t.min_len, t.adapter_len, {}};
-        for (int i = 0; i < 64; i++) out->adapter[i >> 2] |= (uint32_t)t.adapter[i] << (8 * (i & 3));
-    }
-    return true;
-}
-
-static bool readtrim_bufs_ok(const PpgReadTrim &t, const uint32_t *mask, int64_t rec_cap, const void *rows, int64_t rows_cap) {
-    if (!seqquery_mask_ok(mask, rec_cap) || ((t.ops & 0x100) && !mask)) return false;
-    return rows_cap >= 0 && ((uintptr_t)rows & 7) == 0 && (rows != nullptr || rows_cap == 0);
-}
-
-int shard_read_trim(ppg_shard *sh, int32_t b0, int32_t b1, const uint32_t *recs, int64_t rec0, int64_t tot,
-                    const PpgReadTrim &trm, uint32_t *mask, uint32_t *rows, bool first, bool laid_out) {
-    hipStream_t s = shard_stream(sh);
-    const int nb = b1 - b0;
-    if (!readtrim_linked()) return PPG_UNSUPPORTED;
-    int64_t total = sh->sq_total;
-    if (!laid_out) {
-        if (int rc = shard_seq_layout(sh, b0, b1, recs, &total)) return rc;
-        sh->sq_total = total;
-        HIPCHK(grow_buf(sh->sq_off, (size_t)tot + 1));
-        HIPCHK(grow_buf(sh->sq_len, (size_t)tot + 1));
-        HIPCHK(ppg_launch_seq_offsets(s, sh->res.p + b0, sh->info.p + b0, sh->base.p + b0, recs, sh->sp_cbase.p, 0,
-                                      sh->sq_off.p, sh->sq_len.p, nb));
-    }
-    HIPCHK(grow_buf(sh->rt_rsc, 4 * ((size_t)tot + 1)));
-    HIPCHK(sh->rt_acc.alloc(kRtAcc));
-    HIPCHK(sh->rt_host.alloc(8 * ((size_t)kRtAcc + (size_t)sh->n)));
-    if (first) HIPCHK(hipMemsetAsync(sh->rt_acc.p, 0, 8 * (size_t)kRtAcc, s));
-    if (tot) {   // "none found": all ones for the three minima, 0 for the maximum
-        HIPCHK(hipMemsetAsync(sh->rt_rsc.p, 0xFF, 12 * (size_t)tot, s));
-        HIPCHK(hipMemsetAsync(sh->rt_rsc.p + 3 * (size_t)tot, 0, 4 * (size_t)tot, s));
-    }
-    if (mask && !(trm.ops & 0x100)) {   // as the filter: this batch's words; AND_MASK changes its bits alone
-        const uint64_t w0 = ((uint64_t)rec0 + 31) / 32, w1 = ((uint64_t)rec0 + (uint64_t)tot + 31) / 32;
-        if (w1 > w0) HIPCHK(hipMemsetAsync(mask + w0, 0, 4 * (size_t)(w1 - w0), s));
-    }
-    HIPCHK(ppg_launch_rt_measure(s, sh->out.p, sh->jobs.p + b0, sh->offs.p, sh->oref.p + b0, sh->info.p + b0,
-                                 sh->base.p + b0, recs, sh->sp_cbase.p, sh->sq_off.p, sh->sq_len.p, (uint64_t)total, &trm,
-                                 sh->rt_rsc.p, (uint64_t)tot, nb));
-    int64_t *host = (int64_t *)sh->rt_host.p;
-    HIPCHK(ppg_launch_rt_decide(s, sh->res.p + b0, sh->info.p + b0, sh->base.p + b0, recs, sh->rt_rsc.p, (uint64_t)tot, &trm,
-                                mask, (uint64_t)rec0, rows, sh->rt_acc.p, host + kRtAcc + b0, nb));
-    HIPCHK(ppg_launch_rt_totals(s, sh->rt_acc.p, host));
-    return PPG_OK;
-}
-
-// what the last completed trim left in pinned memory
-void readtrim_outputs(const ppg_shard *sh, int64_t *chunk_kept, void *result) {
-    const int64_t *host = (const int64_t *)sh->rt_host.p;
-    if (!host) {   // a shard without chunks: no batch ran
-        if (result) memset(result, 0, sizeof(ppg_read_trim_result));
-        return;
-    }
-    if (result) memcpy(result, host, sizeof(ppg_read_trim_result));
-    if (chunk_kept && sh->n) memcpy(chunk_kept, host + kRtAcc, 8 * (size_t)sh->n);
-}
-
-// ---- record selection (ppg_seqselect.hip) ----
-int shard_select_reserve(ppg_shard *sh, int64_t nchunks) {
-    HIPCHK(sh->sel_ccnt.alloc(2 * ((size_t)nchunks + 1)));
-    HIPCHK(sh->sel_cbase.alloc(2 * ((size_t)nchunks + 1)));
-    HIPCHK(sh->sel_host.alloc(16));
-    return PPG_OK;
-}
-
-int shard_select_sizes(ppg_shard *sh, int32_t b0, int32_t b1, const uint32_t *recs, const uint32_t *mask, int64_t bit0,
-                       int64_t *records, int64_t *bytes) {
-    hipStream_t s = shard_stream(sh);
-    const int nb = b1 - b0;
-    if (!select_linked()) return PPG_UNSUPPORTED;
-    if (int rc = shard_select_reserve(sh, std::max<int64_t>(nb, sh->n))) return rc;   // once: every batch fits
-    const size_t h = sh->sel_ccnt.n / 2;   // records in the first half, bytes in the second
-    HIPCHK(ppg_launch_sel_count(s, sh->res.p + b0, sh->info.p + b0, sh->base.p + b0, recs, mask, (uint64_t)bit0,
-                                sh->sel_ccnt.p, sh->sel_ccnt.p + h, nb));
-    HIPCHK(ppg_launch_sel_scan(s, sh->sel_ccnt.p, sh->sel_ccnt.p + h, sh->sel_cbase.p, sh->sel_cbase.p + h,
-                               (int64_t *)sh->sel_host.p, nb));
-    HIPCHK(hipStreamSynchronize(s));
-    *records = ((volatile int64_t *)sh->sel_host.p)[0];
-    *bytes = ((volatile int64_t *)sh->sel_host.p)[1];
-    return PPG_OK;
-}
-
-int shard_select_move(ppg_shard *sh, int32_t b0, int32_t b1, const uint32_t *recs, const uint32_t *mask, int64_t bit0,
-                      int64_t rec_lo, int64_t byte_lo, int64_t records, int64_t bytes, int64_t *recno, int64_t *sel_off,
-                      uint32_t *desc, uint8_t *dst) {
-    hipStream_t s = shard_stream(sh);
-    const int nb = b1 - b0;
-    if (!select_linked()) return PPG_UNSUPPORTED;
-    const size_t h = sh->sel_ccnt.n / 2;
-    HIPCHK(grow_buf(sh->sel_src, (size_t)records + 1));
-    HIPCHK(grow_buf(sh->sel_span, (size_t)((byte_lo + bytes) / kSelSpan - byte_lo / kSelSpan) + 2));
-    HIPCHK(ppg_launch_sel_place(s, sh->res.p + b0, sh->info.p + b0, sh->base.p + b0, recs, mask, (uint64_t)bit0,
-                                sh->sel_cbase.p, sh->sel_cbase.p + h, sh->out.p, sh->jobs.p + b0, sh->offs.p, sh->oref.p + b0,
-                                rec_lo, byte_lo, recno, sel_off, desc, sh->sel_src.p, sh->sel_span.p, nb));
-    HIPCHK(ppg_launch_sel_copy(s, sel_off, sh->sel_src.p, sh->sel_span.p, rec_lo, rec_lo + records, byte_lo, byte_lo + bytes,
-                               dst));
-    return PPG_OK;
-}
-
-// batch_collect's hook, the last of a batch's hooks: the batch's selected records are appended
-static int select_hook(ppg_shard *sh, int32_t b0, int32_t b1, int64_t tot) {
-    if (b0 == 0) sh->sel_records = sh->sel_nbytes = 0;   // the run's first batch
-    if (sh->sel_mask && sh->total_records + tot > sh->sel_mask_cap) return PPG_BUF_ERROR;
-    const uint32_t *recs = sh->recs.p + 4 * (uint64_t)sh->total_records;
-    int64_t S = 0, B = 0;
-    if (int rc = shard_select_sizes(sh, b0, b1, recs, sh->sel_mask, sh->total_records, &S, &B)) return rc;
-    if (sh->sel_records + S > sh->sel_cap || sh->sel_nbytes + B > sh->sel_byte_cap) return PPG_BUF_ERROR;
-    if (int rc = shard_select_move(sh, b0, b1, recs, sh->sel_mask, sh->total_records, sh->sel_records, sh->sel_nbytes, S, B,
-                                   sh->sel_recno, sh->sel_off, sh->sel_desc, sh->sel_bytes))
-        return rc;
-    sh->sel_records += S;
-    sh->sel_nbytes += B;
-    return PPG_OK;
-}
-
 // Enqueue one batch [b0, b1) on the shard's stream, with no host synchronisation: inflate (+ the
 // fused newline census), per-chunk counts and their scan, the record total into pinned host
 // memory, then the descriptors, whose writes stop at the descriptor buffer's size.
@@ -1045,46 +702,8 @@ int batch_collect(ppg_shard *sh, int32_t b0, int32_t b1, float &total_ms) {
         HIPCHK(hipEventElapsedTime(&c2, sh->ev[2], sh->ev[3]));
         c += c2;
     }
-    // spot keys of the batch's records while its output is resident (ppg_shard_set_keys); the next
-    // batch's inflate follows on the same stream, so this output is read before it is overwritten
-    if (sh->keys_dev) {
-        if (sh->total_records + (int64_t)tot > sh->keys_cap) return PPG_BUF_ERROR;
-        HIPCHK(ppg_launch_record_keys(s, sh->out.p, sh->jobs.p + b0, sh->res.p + b0, sh->offs.p, sh->oref.p + b0,
-                                      sh->info.p + b0, sh->base.p + b0, sh->recs.p + r0,
-                                      sh->keys_dev + sh->total_records, nb));
-    }
-    // packed reads of the batch, likewise while its output is resident (ppg_shard_set_seqpack)
-    if (sh->sp_off)
-        if (int rc = seq_hook(sh, b0, b1, (int64_t)tot)) return rc;
-    // sequence query of the batch, likewise (ppg_shard_set_seqquery)
-    if (sh->sq_on) {
-        if (sh->sq_mask && sh->total_records + (int64_t)tot > sh->sq_rec_cap) return PPG_BUF_ERROR;
-        if (int rc = shard_seq_query(sh, b0, b1, sh->recs.p + r0, sh->total_records, (int64_t)tot, sh->sq_pat, sh->sq_m,
-                                     sh->sq_mask, b0 == 0))
-            return rc;
-    }
-    // read filter of the batch, likewise, after the query: with AND_MASK on the query's mask it sees
-    // this batch's hit bits (ppg_shard_set_readfilter)
-    if (sh->rf_on) {
-        const int64_t after = sh->total_records + (int64_t)tot;
-        if ((sh->rf_mask && after > sh->rf_rec_cap) || (sh->rf_metrics && after > sh->rf_metrics_cap)) return PPG_BUF_ERROR;
-        if (int rc = shard_read_filter(sh, b0, b1, sh->recs.p + r0, sh->total_records, (int64_t)tot, sh->rf_flt, sh->rf_mask,
-                                       sh->rf_metrics, b0 == 0, sh->sq_on != 0))
-            return rc;
-    }
-    // read trim of the batch, likewise, after the filter: with AND_MASK it sees what the query and the
-    // filter have left of this batch's bits (ppg_shard_set_readtrim)
-    if (sh->rt_on) {
-        const int64_t after = sh->total_records + (int64_t)tot;
-        if ((sh->rt_mask && after > sh->rt_rec_cap) || (sh->rt_rows && after > sh->rt_rows_cap)) return PPG_BUF_ERROR;
-        if (int rc = shard_read_trim(sh, b0, b1, sh->recs.p + r0, sh->total_records, (int64_t)tot, sh->rt_trm, sh->rt_mask,
-                                     sh->rt_rows, b0 == 0, sh->sq_on != 0 || sh->rf_on != 0))
-            return rc;
-    }
-    // selection of the batch's records, likewise and last: a query, filter or trim hook has filled this
-    // batch's bits of a mask they share (ppg_shard_set_select)
-    if (sh->sel_on)
-        if (int rc = select_hook(sh, b0, b1, (int64_t)tot)) return rc;
+    // whatever is attached to the shard runs on the batch while its output is resident (ppg_stages.cpp)
+    if (int rc = shard_batch_hooks(sh, b0, b1, (int64_t)tot)) return rc;
     sh->t_inflate += a;
     sh->t_parse += b + c;
     total_ms += a + b + c;
@@ -1131,19 +750,9 @@ static int shard_run(ppg_shard *sh) {
 
 int ppg_shard_run(ppg_shard *sh) {
     if (!sh) return PPG_ARG_ERROR;
-    sh->keys_written = 0;
-    sh->sp_written = 0;
-    sh->sq_written = 0;
-    sh->rf_written = 0;
-    sh->rt_written = 0;
-    sh->sel_written = 0;
+    stages_run_begin(sh);
     sh->last_rc = shard_run(sh);
-    sh->keys_written = sh->last_rc == PPG_OK && sh->keys_dev != nullptr;
-    sh->sp_written = sh->last_rc == PPG_OK && sh->sp_off != nullptr;
-    sh->sq_written = sh->last_rc == PPG_OK && sh->sq_on;
-    sh->rf_written = sh->last_rc == PPG_OK && sh->rf_on;
-    sh->rt_written = sh->last_rc == PPG_OK && sh->rt_on;
-    sh->sel_written = sh->last_rc == PPG_OK && sh->sel_on;
+    stages_run_end(sh, sh->last_rc == PPG_OK);
     return sh->last_rc;
 }
 
@@ -1357,624 +966,6 @@ int ppg_shard_keys(ppg_shard *sh, int64_t *dev_keys, int64_t cap) {
                                   sh->recs.p, dev_keys, sh->n));
     HIPCHK(hipStreamSynchronize(s));
     return PPG_OK;
-}
-
-// ---- packed reads: the keys entry points' counterparts ----
-static bool seq_args_ok(const int64_t *off, const uint32_t *len, int64_t rec_cap, const uint32_t *bases,
-                        const uint32_t *mask, const uint8_t *qual, int64_t base_cap) {
-    // a unit is stored as one 8-B word of bases and 32 B of qualities: the planes' alignment
-    return off && len && bases && mask && rec_cap >= 0 && base_cap >= 0 && base_cap % 32 == 0 &&
-           ((uintptr_t)off & 7) == 0 && ((uintptr_t)len & 3) == 0 && ((uintptr_t)bases & 7) == 0 &&
-           ((uintptr_t)mask & 3) == 0 && ((uintptr_t)qual & 15) == 0;
-}
-
-int ppg_shard_seq_bases(ppg_shard *sh, int64_t *total_bases, int64_t *records) {
-    if (!sh || !sh->ran) return PPG_ARG_ERROR;
-    if (!seq_linked()) return PPG_UNSUPPORTED;
-    HIPCHK(hipSetDevice(sh->ctx->device));
-    hipStream_t s = shard_stream(sh);
-    if (int rc = shard_seq_reserve(sh, sh->n)) return rc;
-    // every batch's descriptors are resident, each with record bases relative to its own first record
-    for (auto [b0, b1] : sh->batches)
-        HIPCHK(ppg_launch_seq_totals(s, sh->res.p + b0, sh->info.p + b0, sh->base.p + b0,
-                                     sh->recs.p + 4 * (uint64_t)sh->h_base[(size_t)b0], sh->sp_ctot.p + b0, b1 - b0));
-    HIPCHK(ppg_launch_seq_scan(s, sh->sp_ctot.p, sh->sp_cbase.p, (uint64_t *)sh->sp_htot.p, sh->n));
-    HIPCHK(hipStreamSynchronize(s));
-    if (total_bases) *total_bases = (int64_t)*(volatile uint64_t *)sh->sp_htot.p;
-    if (records) *records = sh->total_records;
-    return PPG_OK;
-}
-
-int ppg_shard_pack_seq(ppg_shard *sh, int64_t *dev_seq_off, uint32_t *dev_seq_len, int64_t rec_cap,
-                       uint32_t *dev_bases, uint32_t *dev_mask, uint8_t *dev_qual, int64_t base_cap,
-                       int64_t *total_bases) {
-    if (!sh || !sh->ran || sh->batches.size() != 1 ||
-        !seq_args_ok(dev_seq_off, dev_seq_len, rec_cap, dev_bases, dev_mask, dev_qual, base_cap))
-        return PPG_ARG_ERROR;
-    HIPCHK(hipSetDevice(sh->ctx->device));
-    int64_t total = 0;
-    if (int rc = shard_seq_layout(sh, 0, sh->n, sh->recs.p, &total)) return rc;
-    if (total_bases) *total_bases = total;
-    if (sh->total_records > rec_cap || total > base_cap) return PPG_BUF_ERROR;
-    if (int rc = shard_seq_pack(sh, 0, sh->n, sh->recs.p, 0, total, dev_seq_off, dev_seq_len, dev_bases, dev_mask,
-                                dev_qual))
-        return rc;
-    HIPCHK(hipStreamSynchronize(shard_stream(sh)));
-    return PPG_OK;
-}
-
-int ppg_shard_set_seqpack(ppg_shard *sh, int64_t *dev_seq_off, uint32_t *dev_seq_len, int64_t rec_cap,
-                          uint32_t *dev_bases, uint32_t *dev_mask, uint8_t *dev_qual, int64_t base_cap) {
-    if (!sh) return PPG_ARG_ERROR;
-    const bool off = !dev_seq_off && !dev_seq_len && !dev_bases && !dev_mask && !dev_qual && !rec_cap && !base_cap;
-    if (!off && !seq_args_ok(dev_seq_off, dev_seq_len, rec_cap, dev_bases, dev_mask, dev_qual, base_cap))
-        return PPG_ARG_ERROR;
-    sh->sp_off = dev_seq_off;
-    sh->sp_len = dev_seq_len;
-    sh->sp_bases = dev_bases;
-    sh->sp_mask = dev_mask;
-    sh->sp_qual = dev_qual;
-    sh->sp_rec_cap = rec_cap;
-    sh->sp_base_cap = base_cap;
-    sh->sp_written = 0;   // filled by the next run, not by an earlier one
-    return PPG_OK;
-}
-
-int ppg_shard_seqpack_ready(ppg_shard *sh, int64_t *total_bases) {
-    if (!sh) return PPG_ARG_ERROR;
-    if (!sh->sp_written) return 0;
-    if (total_bases) *total_bases = sh->sp_total;
-    return 1;
-}
-
-// ---- sequence queries: the packed reads entry points' counterparts ----
-int ppg_shard_query_seq(ppg_shard *sh, const uint8_t *pattern, int32_t pattern_len, uint32_t *dev_hit_mask,
-                        int64_t rec_cap, int64_t *chunk_hits, void *result) {
-    PpgSeqPattern pat;
-    if (!sh || !sh->ran || sh->batches.size() != 1 || !seqquery_pattern(pattern, pattern_len, &pat) ||
-        !seqquery_mask_ok(dev_hit_mask, rec_cap))
-        return PPG_ARG_ERROR;
-    if (!seqquery_linked()) return PPG_UNSUPPORTED;
-    if (dev_hit_mask && sh->total_records > rec_cap) return PPG_BUF_ERROR;
-    HIPCHK(hipSetDevice(sh->ctx->device));
-    sh->sq_written = 0;   // the pinned outputs are rewritten: an earlier run's hook result is gone
-    if (int rc = shard_seq_query(sh, 0, sh->n, sh->recs.p, 0, sh->total_records, pat, pattern_len, dev_hit_mask, true))
-        return rc;
-    HIPCHK(hipStreamSynchronize(shard_stream(sh)));
-    seqquery_outputs(sh, chunk_hits, result);
-    return PPG_OK;
-}
-
-int ppg_shard_set_seqquery(ppg_shard *sh, const uint8_t *pattern, int32_t pattern_len, uint32_t *dev_hit_mask,
-                           int64_t rec_cap) {
-    if (!sh) return PPG_ARG_ERROR;
-    const bool off = !pattern && pattern_len < 0 && !dev_hit_mask && !rec_cap;
-    PpgSeqPattern pat = {};
-    if (!off && (!seqquery_pattern(pattern, pattern_len, &pat) || !seqquery_mask_ok(dev_hit_mask, rec_cap)))
-        return PPG_ARG_ERROR;
-    sh->sq_on = off ? 0 : 1;
-    sh->sq_pat = pat;
-    sh->sq_m = off ? 0 : pattern_len;
-    sh->sq_mask = dev_hit_mask;
-    sh->sq_rec_cap = rec_cap;
-    sh->sq_written = 0;   // completed by the next run, not by an earlier one
-    return PPG_OK;
-}
-
-int ppg_shard_seqquery_ready(ppg_shard *sh, int64_t *chunk_hits, void *result) {
-    if (!sh) return PPG_ARG_ERROR;
-    if (!sh->sq_written) return 0;
-    seqquery_outputs(sh, chunk_hits, result);
-    return 1;
-}
-
-// ---- read filters: the sequence queries entry points' counterparts ----
-int ppg_read_filter_check(const void *filter) { return readfilter_ok(filter, nullptr) ? PPG_OK : PPG_ARG_ERROR; }
-
-int ppg_shard_filter_reads(ppg_shard *sh, const void *filter, uint32_t *dev_pass_mask, int64_t rec_cap, void *dev_metrics,
-                           int64_t metrics_cap, int64_t *chunk_passed, void *result) {
-    PpgReadFilter flt;
-    if (!sh || !sh->ran || sh->batches.size() != 1 || !readfilter_ok(filter, &flt) ||
-        !readfilter_bufs_ok(flt, dev_pass_mask, rec_cap, (const uint8_t *)dev_metrics, metrics_cap))
-        return PPG_ARG_ERROR;
-    if (!readfilter_linked()) return PPG_UNSUPPORTED;
-    if ((dev_pass_mask && sh->total_records > rec_cap) || (dev_metrics && sh->total_records > metrics_cap))
-        return PPG_BUF_ERROR;
-    HIPCHK(hipSetDevice(sh->ctx->device));
-    sh->rf_written = 0;   // the pinned outputs are rewritten: an earlier run's hook result is gone
-    if (int rc = shard_read_filter(sh, 0, sh->n, sh->recs.p, 0, sh->total_records, flt, dev_pass_mask,
-                                   (uint8_t *)dev_metrics, true, false))
-        return rc;
-    HIPCHK(hipStreamSynchronize(shard_stream(sh)));
-    readfilter_outputs(sh, chunk_passed, result);
-    return PPG_OK;
-}
-
-int ppg_shard_set_readfilter(ppg_shard *sh, const void *filter, uint32_t *dev_pass_mask, int64_t rec_cap, void *dev_metrics,
-                             int64_t metrics_cap) {
-    if (!sh) return PPG_ARG_ERROR;
-    PpgReadFilter flt = {};
-    if (filter && (!readfilter_ok(filter, &flt) ||
-                   !readfilter_bufs_ok(flt, dev_pass_mask, rec_cap, (const uint8_t *)dev_metrics, metrics_cap)))
-        return PPG_ARG_ERROR;
-    sh->rf_on = filter ? 1 : 0;
-    sh->rf_flt = flt;
-    sh->rf_mask = filter ? dev_pass_mask : nullptr;
-    sh->rf_rec_cap = filter ? rec_cap : 0;
-    sh->rf_metrics = filter ? (uint8_t *)dev_metrics : nullptr;
-    sh->rf_metrics_cap = filter ? metrics_cap : 0;
-    sh->rf_written = 0;   // completed by the next run, not by an earlier one
-    return PPG_OK;
-}
-
-int ppg_shard_readfilter_ready(ppg_shard *sh, int64_t *chunk_passed, void *result) {
-    if (!sh) return PPG_ARG_ERROR;
-    if (!sh->rf_written) return 0;
-    readfilter_outputs(sh, chunk_passed, result);
-    return 1;
-}
-
-// ---- read trimming: the read filters entry points' counterparts ----
-int ppg_read_trim_check(const void *trim) { return readtrim_ok(trim, nullptr) ? PPG_OK : PPG_ARG_ERROR; }
-
-int ppg_shard_trim_reads(ppg_shard *sh, const void *trim, uint32_t *dev_keep_mask, int64_t rec_cap, void *dev_trim,
-                         int64_t trim_cap, int64_t *chunk_kept, void *result) {
-    PpgReadTrim trm;
-    if (!sh || !sh->ran || sh->batches.size() != 1 || !readtrim_ok(trim, &trm) ||
-        !readtrim_bufs_ok(trm, dev_keep_mask, rec_cap, dev_trim, trim_cap))
-        return PPG_ARG_ERROR;
-    if (!readtrim_linked()) return PPG_UNSUPPORTED;
-    if ((dev_keep_mask && sh->total_records > rec_cap) || (dev_trim && sh->total_records > trim_cap)) return PPG_BUF_ERROR;
-    HIPCHK(hipSetDevice(sh->ctx->device));
-    sh->rt_written = 0;   // the pinned outputs are rewritten: an earlier run's hook result is gone
-    if (int rc = shard_read_trim(sh, 0, sh->n, sh->recs.p, 0, sh->total_records, trm, dev_keep_mask, (uint32_t *)dev_trim, true,
-                                 false))
-        return rc;
-    HIPCHK(hipStreamSynchronize(shard_stream(sh)));
-    readtrim_outputs(sh, chunk_kept, result);
-    return PPG_OK;
-}
-
-int ppg_shard_set_readtrim(ppg_shard *sh, const void *trim, uint32_t *dev_keep_mask, int64_t rec_cap, void *dev_trim,
-                           int64_t trim_cap) {
-    if (!sh) return PPG_ARG_ERROR;
-    PpgReadTrim trm = {};
-    if (trim && (!readtrim_ok(trim, &trm) || !readtrim_bufs_ok(trm, dev_keep_mask, rec_cap, dev_trim, trim_cap)))
-        return PPG_ARG_ERROR;
-    sh->rt_on = trim ? 1 : 0;
-    sh->rt_trm = trm;
-    sh->rt_mask = trim ? dev_keep_mask : nullptr;
-    sh->rt_rec_cap = trim ? rec_cap : 0;
-    sh->rt_rows = trim ? (uint32_t *)dev_trim : nullptr;
-    sh->rt_rows_cap = trim ? trim_cap : 0;
-    sh->rt_written = 0;   // completed by the next run, not by an earlier one
-    return PPG_OK;
-}
-
-int ppg_shard_readtrim_ready(ppg_shard *sh, int64_t *chunk_kept, void *result) {
-    if (!sh) return PPG_ARG_ERROR;
-    if (!sh->rt_written) return 0;
-    readtrim_outputs(sh, chunk_kept, result);
-    return 1;
-}
-
-// ---- record selection: the sequence queries entry points' counterparts ----
-static bool select_bufs_ok(const int64_t *recno, const int64_t *sel_off, const uint32_t *desc, int64_t sel_cap,
-                           const uint8_t *bytes, int64_t byte_cap) {
-    // a descriptor is stored as one 16-B word, the text in 16-B words
-    return recno && sel_off && desc && bytes && sel_cap >= 0 && byte_cap >= 0 && ((uintptr_t)recno & 7) == 0 &&
-           ((uintptr_t)sel_off & 7) == 0 && ((uintptr_t)desc & 15) == 0 && ((uintptr_t)bytes & 15) == 0;
-}
-
-int ppg_shard_select_size(ppg_shard *sh, const uint32_t *dev_mask, int64_t mask_cap, int64_t *records, int64_t *bytes) {
-    if (!sh || !sh->ran || !seqquery_mask_ok(dev_mask, mask_cap)) return PPG_ARG_ERROR;
-    if (!select_linked()) return PPG_UNSUPPORTED;
-    if (dev_mask && sh->total_records > mask_cap) return PPG_BUF_ERROR;
-    HIPCHK(hipSetDevice(sh->ctx->device));
-    hipStream_t s = shard_stream(sh);
-    if (int rc = shard_select_reserve(sh, sh->n)) return rc;
-    const size_t h = sh->sel_ccnt.n / 2;
-    // every batch's descriptors are resident, each with record bases relative to its own first record
-    for (auto [b0, b1] : sh->batches) {
-        const uint64_t r0 = (uint64_t)sh->h_base[(size_t)b0];
-        HIPCHK(ppg_launch_sel_count(s, sh->res.p + b0, sh->info.p + b0, sh->base.p + b0, sh->recs.p + 4 * r0, dev_mask, r0,
-                                    sh->sel_ccnt.p + b0, sh->sel_ccnt.p + h + b0, b1 - b0));
-    }
-    HIPCHK(ppg_launch_sel_scan(s, sh->sel_ccnt.p, sh->sel_ccnt.p + h, sh->sel_cbase.p, sh->sel_cbase.p + h,
-                               (int64_t *)sh->sel_host.p, sh->batches.empty() ? 0 : sh->n));
-    HIPCHK(hipStreamSynchronize(s));
-    if (records) *records = ((volatile int64_t *)sh->sel_host.p)[0];
-    if (bytes) *bytes = ((volatile int64_t *)sh->sel_host.p)[1];
-    return PPG_OK;
-}
-
-int ppg_shard_select_records(ppg_shard *sh, const uint32_t *dev_mask, int64_t mask_cap, int64_t *dev_recno,
-                             int64_t *dev_sel_off, uint32_t *dev_desc, int64_t sel_cap, uint8_t *dev_bytes,
-                             int64_t byte_cap, int64_t *records, int64_t *bytes) {
-    if (!sh || !sh->ran || sh->batches.size() != 1 || !seqquery_mask_ok(dev_mask, mask_cap) ||
-        !select_bufs_ok(dev_recno, dev_sel_off, dev_desc, sel_cap, dev_bytes, byte_cap))
-        return PPG_ARG_ERROR;
-    if (!select_linked()) return PPG_UNSUPPORTED;
-    if (dev_mask && sh->total_records > mask_cap) return PPG_BUF_ERROR;
-    HIPCHK(hipSetDevice(sh->ctx->device));
-    int64_t S = 0, B = 0;
-    if (int rc = shard_select_sizes(sh, 0, sh->n, sh->recs.p, dev_mask, 0, &S, &B)) return rc;
-    if (records) *records = S;
-    if (bytes) *bytes = B;
-    if (S > sel_cap || B > byte_cap) return PPG_BUF_ERROR;   // before the movers: nothing is written
-    if (int rc = shard_select_move(sh, 0, sh->n, sh->recs.p, dev_mask, 0, 0, 0, S, B, dev_recno, dev_sel_off, dev_desc,
-                                   dev_bytes))
-        return rc;
-    HIPCHK(hipStreamSynchronize(shard_stream(sh)));
-    return PPG_OK;
-}
-
-int ppg_shard_set_select(ppg_shard *sh, const uint32_t *dev_mask, int64_t mask_cap, int64_t *dev_recno,
-                         int64_t *dev_sel_off, uint32_t *dev_desc, int64_t sel_cap, uint8_t *dev_bytes, int64_t byte_cap) {
-    if (!sh) return PPG_ARG_ERROR;
-    const bool off = !dev_mask && !mask_cap && !dev_recno && !dev_sel_off && !dev_desc && !sel_cap && !dev_bytes && !byte_cap;
-    if (!off && (!seqquery_mask_ok(dev_mask, mask_cap) ||
-                 !select_bufs_ok(dev_recno, dev_sel_off, dev_desc, sel_cap, dev_bytes, byte_cap)))
-        return PPG_ARG_ERROR;
-    sh->sel_on = off ? 0 : 1;
-    sh->sel_mask = dev_mask;
-    sh->sel_mask_cap = mask_cap;
-    sh->sel_recno = dev_recno;
-    sh->sel_off = dev_sel_off;
-    sh->sel_desc = dev_desc;
-    sh->sel_bytes = dev_bytes;
-    sh->sel_cap = sel_cap;
-    sh->sel_byte_cap = byte_cap;
-    sh->sel_written = 0;   // completed by the next run, not by an earlier one
-    return PPG_OK;
-}
-
-int ppg_shard_select_ready(ppg_shard *sh, int64_t *records, int64_t *bytes) {
-    if (!sh) return PPG_ARG_ERROR;
-    if (!sh->sel_written) return 0;
-    if (records) *records = sh->sel_records;
-    if (bytes) *bytes = sh->sel_nbytes;
-    return 1;
-}
-
-// Measurement hook of tools/seqselect_probe.py (not part of the ABI: no declaration in ppgpu.h).  On a
-// one-batch shard after its run, device time by hipEvents on the shard's stream, the median of reps
-// launches after one warm-up each, into ms[0..4]: count, scan, place, copy, and ppg_pack_raw of the same
-// batch (which moves every text byte once, as a selection of every record does); sizes[0..2]: the
-// selected records, their bytes and the raw text's bytes.  The buffers are the hook's own.
-int ppgx_seqselect_times(ppg_shard *sh, const uint32_t *dev_mask, int64_t mask_cap, int reps, float *ms, int64_t *sizes) {
-    if (!sh || !sh->ran || sh->batches.size() != 1 || !ms || !sizes || reps < 1 || !seqquery_mask_ok(dev_mask, mask_cap) ||
-        (dev_mask && sh->total_records > mask_cap))
-        return PPG_ARG_ERROR;
-    HIPCHK(hipSetDevice(sh->ctx->device));
-    hipStream_t s = shard_stream(sh);
-    int64_t S = 0, B = 0;
-    if (int rc = shard_select_sizes(sh, 0, sh->n, sh->recs.p, dev_mask, 0, &S, &B)) return rc;
-    std::vector<int64_t> raw_off((size_t)sh->n + 1, 0);
-    for (int32_t k = 0; k < sh->n; k++)
-        raw_off[(size_t)k + 1] = raw_off[(size_t)k] + (int64_t)sh->h_jobs[(size_t)k].raw_shift + (int64_t)sh->h_res[(size_t)k].produced;
-    DevBuf<int64_t> recno, off, draw;
-    DevBuf<uint32_t> desc;
-    DevBuf<uint8_t> dst, text;
-    HIPCHK(recno.alloc((size_t)S));
-    HIPCHK(off.alloc((size_t)S + 1));
-    HIPCHK(desc.alloc(4 * (size_t)S));
-    HIPCHK(dst.alloc((size_t)B + 16));
-    HIPCHK(text.alloc((size_t)raw_off[(size_t)sh->n]));
-    HIPCHK(draw.alloc(raw_off.size()));
-    HIPCHK(hipMemcpyAsync(draw.p, raw_off.data(), 8 * raw_off.size(), hipMemcpyHostToDevice, s));
-    // one whole move first: it sizes the scratch and leaves sel_off / the scratch in place for the copy
-    if (int rc = shard_select_move(sh, 0, sh->n, sh->recs.p, dev_mask, 0, 0, 0, S, B, recno.p, off.p, desc.p, dst.p)) return rc;
-    HIPCHK(hipStreamSynchronize(s));
-    const size_t h = sh->sel_ccnt.n / 2;
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    HIPCHK(hipEventCreate(&e0));
-    HIPCHK(hipEventCreate(&e1));
-    int rc = PPG_OK;
-    for (int what = 0; what < 5 && rc == PPG_OK; what++) {
-        std::vector<float> t;
-        for (int r = 0; r <= reps && rc == PPG_OK; r++) {
-            hipError_t e = hipEventRecord(e0, s);
-            if (e == hipSuccess && what == 0) {
-                e = ppg_launch_sel_count(s, sh->res.p, sh->info.p, sh->base.p, sh->recs.p, dev_mask, 0, sh->sel_ccnt.p,
-                                         sh->sel_ccnt.p + h, sh->n);
-            } else if (e == hipSuccess && what == 1) {
-                e = ppg_launch_sel_scan(s, sh->sel_ccnt.p, sh->sel_ccnt.p + h, sh->sel_cbase.p, sh->sel_cbase.p + h,
-                                        (int64_t *)sh->sel_host.p, sh->n);
-            } else if (e == hipSuccess && what == 2) {
-                e = ppg_launch_sel_place(s, sh->res.p, sh->info.p, sh->base.p, sh->recs.p, dev_mask, 0, sh->sel_cbase.p,
-                                         sh->sel_cbase.p + h, sh->out.p, sh->jobs.p, sh->offs.p, sh->oref.p, 0, 0, recno.p, off.p,
-                                         desc.p, sh->sel_src.p, sh->sel_span.p, sh->n);
-            } else if (e == hipSuccess && what == 3) {
-                e = ppg_launch_sel_copy(s, off.p, sh->sel_src.p, sh->sel_span.p, 0, S, 0, B, dst.p);
-            } else if (e == hipSuccess) {
-                e = ppg_launch_pack_raw(s, sh->out.p, sh->jobs.p, sh->res.p, sh->offs.p, sh->oref.p, draw.p, text.p, sh->n, 0);
-            }
-            if (e == hipSuccess) e = hipEventRecord(e1, s);
-            if (e == hipSuccess) e = hipEventSynchronize(e1);
-            float v = 0;
-            if (e == hipSuccess) e = hipEventElapsedTime(&v, e0, e1);
-            if (e != hipSuccess) rc = PPG_DEVICE_ERROR;
-            if (r) t.push_back(v);   // (r = 0 warms up)
-        }
-        if (rc == PPG_OK) {
-            std::sort(t.begin(), t.end());
-            ms[what] = t[t.size() / 2];
-        }
-    }
-    (void)hipEventDestroy(e0);
-    (void)hipEventDestroy(e1);
-    sizes[0] = S;
-    sizes[1] = B;
-    sizes[2] = raw_off[(size_t)sh->n];
-    return rc;
-}
-
-// Measurement hook of tools/seqpack_probe.py (not part of the ABI: no declaration in ppgpu.h).  On a
-// one-batch shard after its run, device time by hipEvents on the shard's stream, the median of reps
-// launches after one warm-up each, into ms[0..3]: layout totals + scan, seq_off / seq_len, the pack
-// (qualities when quality != 0), and ppg_pack_raw of the same batch (the text cursor's kernel, which
-// reads the same bytes and writes all of them); bytes[0..1]: the planes' and the raw text's sizes.
-int ppgx_seqpack_times(ppg_shard *sh, int quality, int reps, float *ms, int64_t *bytes) {
-    if (!sh || !sh->ran || sh->batches.size() != 1 || !ms || !bytes || reps < 1) return PPG_ARG_ERROR;
-    HIPCHK(hipSetDevice(sh->ctx->device));
-    hipStream_t s = shard_stream(sh);
-    int64_t total = 0;
-    if (int rc = shard_seq_layout(sh, 0, sh->n, sh->recs.p, &total)) return rc;
-    const int64_t nrec = sh->total_records;
-    std::vector<int64_t> raw_off((size_t)sh->n + 1, 0);
-    for (int32_t k = 0; k < sh->n; k++)
-        raw_off[(size_t)k + 1] = raw_off[(size_t)k] + (int64_t)sh->h_jobs[(size_t)k].raw_shift + (int64_t)sh->h_res[(size_t)k].produced;
-    DevBuf<int64_t> off, draw;
-    DevBuf<uint32_t> len, bases, mask;
-    DevBuf<uint8_t> qual, text;
-    HIPCHK(off.alloc((size_t)nrec + 1));
-    HIPCHK(len.alloc((size_t)nrec));
-    HIPCHK(bases.alloc((size_t)total / 16));
-    HIPCHK(mask.alloc((size_t)total / 32));
-    if (quality) HIPCHK(qual.alloc((size_t)total));
-    HIPCHK(text.alloc((size_t)raw_off[(size_t)sh->n]));
-    HIPCHK(draw.alloc(raw_off.size()));
-    HIPCHK(hipMemcpyAsync(draw.p, raw_off.data(), 8 * raw_off.size(), hipMemcpyHostToDevice, s));
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    HIPCHK(hipEventCreate(&e0));
-    HIPCHK(hipEventCreate(&e1));
-    int rc = PPG_OK;
-    for (int what = 0; what < 4 && rc == PPG_OK; what++) {
-        std::vector<float> t;
-        for (int r = 0; r <= reps && rc == PPG_OK; r++) {
-            hipError_t e = hipEventRecord(e0, s);
-            if (e == hipSuccess && what == 0) {
-                e = ppg_launch_seq_totals(s, sh->res.p, sh->info.p, sh->base.p, sh->recs.p, sh->sp_ctot.p, sh->n);
-                if (e == hipSuccess) e = ppg_launch_seq_scan(s, sh->sp_ctot.p, sh->sp_cbase.p, (uint64_t *)sh->sp_htot.p, sh->n);
-            } else if (e == hipSuccess && what == 1) {
-                e = ppg_launch_seq_offsets(s, sh->res.p, sh->info.p, sh->base.p, sh->recs.p, sh->sp_cbase.p, 0, off.p, len.p,
-                                           sh->n);
-            } else if (e == hipSuccess && what == 2) {
-                e = ppg_launch_seq_pack(s, sh->out.p, sh->jobs.p, sh->res.p, sh->offs.p, sh->oref.p, sh->info.p, sh->base.p,
-                                        sh->recs.p, sh->sp_cbase.p, off.p, len.p, 0, (uint64_t)total, bases.p, mask.p,
-                                        quality ? qual.p : nullptr, sh->n);
-            } else if (e == hipSuccess) {
-                e = ppg_launch_pack_raw(s, sh->out.p, sh->jobs.p, sh->res.p, sh->offs.p, sh->oref.p, draw.p, text.p, sh->n, 0);
-            }
-            if (e == hipSuccess) e = hipEventRecord(e1, s);
-            if (e == hipSuccess) e = hipEventSynchronize(e1);
-            float v = 0;
-            if (e == hipSuccess) e = hipEventElapsedTime(&v, e0, e1);
-            if (e != hipSuccess) rc = PPG_DEVICE_ERROR;
-            if (r) t.push_back(v);   // (r = 0 warms up)
-        }
-        if (rc == PPG_OK) {
-            std::sort(t.begin(), t.end());
-            ms[what] = t[t.size() / 2];
-        }
-    }
-    (void)hipEventDestroy(e0);
-    (void)hipEventDestroy(e1);
-    bytes[0] = total / 4 + total / 8 + (quality ? total : 0) + 12 * nrec + 8;
-    bytes[1] = raw_off[(size_t)sh->n];
-    return rc;
-}
-
-// Measurement hook of tools/seqquery_probe.py (not part of the ABI: no declaration in ppgpu.h).  On a
-// one-batch shard after its run, device time by hipEvents on the shard's stream, the median of reps
-// launches after one warm-up each, into ms[0..3]: layout totals + scan, seq_off / seq_len, the query
-// kernel (with the clearing of its hit bits when there is a pattern), and the per-chunk reduction +
-// the totals' store.  The accumulators keep adding over the launches: only the times are meaningful.
-int ppgx_seqquery_times(ppg_shard *sh, const uint8_t *pattern, int32_t m, int reps, float *ms) {
-    PpgSeqPattern pat;
-    if (!sh || !sh->ran || sh->batches.size() != 1 || !ms || reps < 1 || !seqquery_pattern(pattern, m, &pat))
-        return PPG_ARG_ERROR;
-    HIPCHK(hipSetDevice(sh->ctx->device));
-    hipStream_t s = shard_stream(sh);
-    // one whole query first: it sizes the scratch buffers and leaves the layout in place
-    const int64_t tot = sh->total_records;
-    if (int rc = shard_seq_query(sh, 0, sh->n, sh->recs.p, 0, tot, pat, m, nullptr, true)) return rc;
-    HIPCHK(hipStreamSynchronize(s));
-    const uint64_t total = *(volatile uint64_t *)sh->sp_htot.p;
-    uint32_t *words = m > 0 ? sh->sq_bits.p : nullptr;
-    int64_t *host = (int64_t *)sh->sq_host.p;
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    HIPCHK(hipEventCreate(&e0));
-    HIPCHK(hipEventCreate(&e1));
-    int rc = PPG_OK;
-    for (int what = 0; what < 4 && rc == PPG_OK; what++) {
-        std::vector<float> t;
-        for (int r = 0; r <= reps && rc == PPG_OK; r++) {
-            hipError_t e = hipEventRecord(e0, s);
-            if (e == hipSuccess && what == 0) {
-                e = ppg_launch_seq_totals(s, sh->res.p, sh->info.p, sh->base.p, sh->recs.p, sh->sp_ctot.p, sh->n);
-                if (e == hipSuccess) e = ppg_launch_seq_scan(s, sh->sp_ctot.p, sh->sp_cbase.p, (uint64_t *)sh->sp_htot.p, sh->n);
-            } else if (e == hipSuccess && what == 1) {
-                e = ppg_launch_seq_offsets(s, sh->res.p, sh->info.p, sh->base.p, sh->recs.p, sh->sp_cbase.p, 0, sh->sq_off.p,
-                                           sh->sq_len.p, sh->n);
-            } else if (e == hipSuccess && what == 2) {
-                if (words) e = hipMemsetAsync(words, 0, 4 * (size_t)((tot + 31) / 32), s);
-                if (e == hipSuccess)
-                    e = ppg_launch_seq_query(s, sh->out.p, sh->jobs.p, sh->offs.p, sh->oref.p, sh->info.p, sh->base.p,
-                                             sh->recs.p, sh->sp_cbase.p, sh->sq_off.p, sh->sq_len.p, total, &pat, m, words, 0,
-                                             sh->sq_acc.p, sh->n);
-            } else if (e == hipSuccess) {
-                e = ppg_launch_seq_query_chunks(s, sh->res.p, sh->info.p, sh->base.p, m, words, 0, sh->sq_acc.p, host + 8, sh->n);
-                if (e == hipSuccess) e = ppg_launch_seq_query_totals(s, sh->sq_acc.p, host);
-            }
-            if (e == hipSuccess) e = hipEventRecord(e1, s);
-            if (e == hipSuccess) e = hipEventSynchronize(e1);
-            float v = 0;
-            if (e == hipSuccess) e = hipEventElapsedTime(&v, e0, e1);
-            if (e != hipSuccess) rc = PPG_DEVICE_ERROR;
-            if (r) t.push_back(v);   // (r = 0 warms up)
-        }
-        if (rc == PPG_OK) {
-            std::sort(t.begin(), t.end());
-            ms[what] = t[t.size() / 2];
-        }
-    }
-    (void)hipEventDestroy(e0);
-    (void)hipEventDestroy(e1);
-    sh->sq_written = 0;   // the pinned outputs no longer belong to a run
-    return rc;
-}
-
-// Measurement hook of tools/readfilter_probe.py (not part of the ABI), as ppgx_seqquery_times: on a
-// one-batch shard after its run, the median of reps launches after one warm-up each, into ms[0..2]: the
-// layout (totals + scan + seq_off / seq_len), the measure kernel with the zeroing of its scratch, and the
-// decide kernel (with the clearing of its mask words) + the totals' store.  with_mask / with_metrics:
-// the decide kernel writes shard scratch planes of that size.  hist: ppg_rf_measure's histogram variant
-// (kRfHistRuns / kRfHistBytes).  The accumulators keep adding over the launches: only the times are meaningful.
-int ppgx_readfilter_times(ppg_shard *sh, const void *filter, int with_mask, int with_metrics, int hist, int reps,
-                          float *ms) {
-    PpgReadFilter flt;
-    if (!sh || !sh->ran || sh->batches.size() != 1 || !ms || reps < 1 || !readfilter_ok(filter, &flt) ||
-        (flt.criteria & 0x100) || (hist != kRfHistRuns && hist != kRfHistBytes))
-        return PPG_ARG_ERROR;
-    HIPCHK(hipSetDevice(sh->ctx->device));
-    hipStream_t s = shard_stream(sh);
-    const int64_t tot = sh->total_records;
-    DevBuf<uint32_t> words;
-    DevBuf<uint8_t> rows;
-    if (with_mask) HIPCHK(words.alloc((size_t)tot / 32 + 1));
-    if (with_metrics) HIPCHK(rows.alloc(24 * (size_t)tot + 8));
-    // one whole filter first: it sizes the scratch buffers and leaves the layout in place
-    const int hist_was = sh->rf_hist;
-    sh->rf_hist = hist;
-    int rc = shard_read_filter(sh, 0, sh->n, sh->recs.p, 0, tot, flt, words.p, rows.p, true, false);
-    sh->rf_hist = hist_was;
-    if (rc != PPG_OK) return rc;
-    HIPCHK(hipStreamSynchronize(s));
-    const uint64_t total = *(volatile uint64_t *)sh->sp_htot.p;
-    int64_t *host = (int64_t *)sh->rf_host.p;
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    HIPCHK(hipEventCreate(&e0));
-    HIPCHK(hipEventCreate(&e1));
-    for (int what = 0; what < 3 && rc == PPG_OK; what++) {
-        std::vector<float> t;
-        for (int r = 0; r <= reps && rc == PPG_OK; r++) {
-            hipError_t e = hipEventRecord(e0, s);
-            if (e == hipSuccess && what == 0) {
-                e = ppg_launch_seq_totals(s, sh->res.p, sh->info.p, sh->base.p, sh->recs.p, sh->sp_ctot.p, sh->n);
-                if (e == hipSuccess) e = ppg_launch_seq_scan(s, sh->sp_ctot.p, sh->sp_cbase.p, (uint64_t *)sh->sp_htot.p, sh->n);
-                if (e == hipSuccess)
-                    e = ppg_launch_seq_offsets(s, sh->res.p, sh->info.p, sh->base.p, sh->recs.p, sh->sp_cbase.p, 0,
-                                               sh->sq_off.p, sh->sq_len.p, sh->n);
-            } else if (e == hipSuccess && what == 1) {
-                if (tot) e = hipMemsetAsync(sh->rf_rsc.p, 0, 16 * (size_t)tot, s);
-                if (e == hipSuccess)
-                    e = ppg_launch_rf_measure(s, sh->out.p, sh->jobs.p, sh->offs.p, sh->oref.p, sh->info.p, sh->base.p,
-                                              sh->recs.p, sh->sp_cbase.p, sh->sq_off.p, sh->sq_len.p, total,
-                                              (uint32_t)(flt.qual_base + flt.low_q), sh->rf_rsc.p, sh->rf_acc.p, sh->n, hist);
-            } else if (e == hipSuccess) {
-                if (words.p) e = hipMemsetAsync(words.p, 0, 4 * (size_t)((tot + 31) / 32), s);
-                if (e == hipSuccess)
-                    e = ppg_launch_rf_decide(s, sh->out.p, sh->jobs.p, sh->res.p, sh->offs.p, sh->oref.p, sh->info.p,
-                                             sh->base.p, sh->recs.p, sh->rf_rsc.p, &flt, words.p, 0, rows.p, sh->rf_acc.p,
-                                             host + kRfAcc, sh->n);
-                if (e == hipSuccess) e = ppg_launch_rf_totals(s, sh->rf_acc.p, host);
-            }
-            if (e == hipSuccess) e = hipEventRecord(e1, s);
-            if (e == hipSuccess) e = hipEventSynchronize(e1);
-            float v = 0;
-            if (e == hipSuccess) e = hipEventElapsedTime(&v, e0, e1);
-            if (e != hipSuccess) rc = PPG_DEVICE_ERROR;
-            if (r) t.push_back(v);   // (r = 0 warms up)
-        }
-        if (rc == PPG_OK) {
-            std::sort(t.begin(), t.end());
-            ms[what] = t[t.size() / 2];
-        }
-    }
-    (void)hipEventDestroy(e0);
-    (void)hipEventDestroy(e1);
-    sh->rf_written = 0;   // the pinned outputs no longer belong to a run
-    return rc;
-}
-
-// Measurement hook of tools/readtrim_probe.py (not part of the ABI), as ppgx_readfilter_times: the median
-// of reps launches after one warm-up each, into ms[0..3]: the layout, the measure kernel without the
-// ADAPTER bit and with the trim's ops as they are (both with the initialisation of the scratch; equal ops
-// when the trim has no adapter), and the decide kernel (with the clearing of its mask words, writing the
-// rows) + the totals' store.  with_mask: the decide kernel writes a scratch mask.
-int ppgx_readtrim_times(ppg_shard *sh, const void *trim, int with_mask, int reps, float *ms) {
-    PpgReadTrim trm;
-    if (!sh || !sh->ran || sh->batches.size() != 1 || !ms || reps < 1 || !readtrim_ok(trim, &trm) || (trm.ops & 0x100))
-        return PPG_ARG_ERROR;
-    HIPCHK(hipSetDevice(sh->ctx->device));
-    hipStream_t s = shard_stream(sh);
-    const int64_t tot = sh->total_records;
-    DevBuf<uint32_t> words, rows;
-    if (with_mask) HIPCHK(words.alloc((size_t)tot / 32 + 1));
-    HIPCHK(rows.alloc(2 * (size_t)tot + 2));
-    // one whole trim first: it sizes the scratch buffers and leaves the layout in place
-    int rc = shard_read_trim(sh, 0, sh->n, sh->recs.p, 0, tot, trm, words.p, rows.p, true, false);
-    if (rc != PPG_OK) return rc;
-    HIPCHK(hipStreamSynchronize(s));
-    const uint64_t total = *(volatile uint64_t *)sh->sp_htot.p;
-    int64_t *host = (int64_t *)sh->rt_host.p;
-    PpgReadTrim plain = trm;
-    plain.ops &= ~(int64_t)8;
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    HIPCHK(hipEventCreate(&e0));
-    HIPCHK(hipEventCreate(&e1));
-    for (int what = 0; what < 4 && rc == PPG_OK; what++) {
-        std::vector<float> t;
-        for (int r = 0; r <= reps && rc == PPG_OK; r++) {
-            hipError_t e = hipEventRecord(e0, s);
-            if (e == hipSuccess && what == 0) {
-                e = ppg_launch_seq_totals(s, sh->res.p, sh->info.p, sh->base.p, sh->recs.p, sh->sp_ctot.p, sh->n);
-                if (e == hipSuccess) e = ppg_launch_seq_scan(s, sh->sp_ctot.p, sh->sp_cbase.p, (uint64_t *)sh->sp_htot.p, sh->n);
-                if (e == hipSuccess)
-                    e = ppg_launch_seq_offsets(s, sh->res.p, sh->info.p, sh->base.p, sh->recs.p, sh->sp_cbase.p, 0,
-                                               sh->sq_off.p, sh->sq_len.p, sh->n);
-            } else if (e == hipSuccess && what < 3) {
-                if (tot) e = hipMemsetAsync(sh->rt_rsc.p, 0xFF, 12 * (size_t)tot, s);
-                if (e == hipSuccess && tot) e = hipMemsetAsync(sh->rt_rsc.p + 3 * (size_t)tot, 0, 4 * (size_t)tot, s);
-                if (e == hipSuccess)
-                    e = ppg_launch_rt_measure(s, sh->out.p, sh->jobs.p, sh->offs.p, sh->oref.p, sh->info.p, sh->base.p,
-                                              sh->recs.p, sh->sp_cbase.p, sh->sq_off.p, sh->sq_len.p, total,
-                                              what == 1 ? &plain : &trm, sh->rt_rsc.p, (uint64_t)tot, sh->n);
-            } else if (e == hipSuccess) {
-                if (words.p) e = hipMemsetAsync(words.p, 0, 4 * (size_t)((tot + 31) / 32), s);
-                if (e == hipSuccess)
-                    e = ppg_launch_rt_decide(s, sh->res.p, sh->info.p, sh->base.p, sh->recs.p, sh->rt_rsc.p, (uint64_t)tot, &trm,
-                                             words.p, 0, rows.p, sh->rt_acc.p, host + kRtAcc, sh->n);
-                if (e == hipSuccess) e = ppg_launch_rt_totals(s, sh->rt_acc.p, host);
-            }
-            if (e == hipSuccess) e = hipEventRecord(e1, s);
-            if (e == hipSuccess) e = hipEventSynchronize(e1);
-            float v = 0;
-            if (e == hipSuccess) e = hipEventElapsedTime(&v, e0, e1);
-            if (e != hipSuccess) rc = PPG_DEVICE_ERROR;
-            if (r) t.push_back(v);   // (r = 0 warms up)
-        }
-        if (rc == PPG_OK) {
-            std::sort(t.begin(), t.end());
-            ms[what] = t[t.size() / 2];
-        }
-    }
-    (void)hipEventDestroy(e0);
-    (void)hipEventDestroy(e1);
-    sh->rt_written = 0;   // the pinned outputs no longer belong to a run
-    return rc;
 }
 
 int ppg_shard_record_base(ppg_shard *sh, int64_t *base) {

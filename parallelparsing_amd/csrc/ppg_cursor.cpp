@@ -356,14 +356,15 @@ struct ppg_cursor {
             // query and select while the batch is resident; only the selection crosses PCIe
             if ((size_t)s.nrec + 1 > s.dsel_off.n)
                 if (int rc = grow_select(s, s.nrec + s.nrec / 4)) return rc;
+            if (int rc = shard_layout(&s.sh, 0, m, s.sh.recs.p, s.nrec)) return rc;   // for the query, the filter and the trim
             if (int rc = shard_seq_query(&s.sh, 0, m, s.sh.recs.p, 0, s.nrec, pat, pat_m, s.dsel_mask.p, true)) return rc;
-            // the filter clears the bits of the hits that fail it, on the layout the query has just made
+            // the filter clears the bits of the hits that fail it
             if (filter)
-                if (int rc = shard_read_filter(&s.sh, 0, m, s.sh.recs.p, 0, s.nrec, flt, s.dsel_mask.p, nullptr, true, true))
+                if (int rc = shard_read_filter(&s.sh, 0, m, s.sh.recs.p, 0, s.nrec, flt, s.dsel_mask.p, nullptr, true))
                     return rc;
             // the trim clears the bits of the records that end up shorter than min_len, and leaves every record's window
             if (trim)
-                if (int rc = shard_read_trim(&s.sh, 0, m, s.sh.recs.p, 0, s.nrec, trm, s.dsel_mask.p, s.dtrim.p, true, true))
+                if (int rc = shard_read_trim(&s.sh, 0, m, s.sh.recs.p, 0, s.nrec, trm, s.dsel_mask.p, s.dtrim.p, true))
                     return rc;
             if (int rc = shard_select_sizes(&s.sh, 0, m, s.sh.recs.p, s.dsel_mask.p, 0, &s.sel_records, &s.sel_nbytes))
                 return rc;
@@ -574,7 +575,7 @@ int ppg_cursor_open_filter(ppg_ctx *ctx, const ppg_index *ix, const char *gz_pat
 
 int ppg_cursor_filter_result(const ppg_cursor *c, void *result) {
     if (!c || !c->filter || !c->cur || !result) return PPG_ARG_ERROR;
-    readfilter_outputs(&c->cur->sh, nullptr, result);
+    c->cur->sh.filter.outputs(c->cur->sh.n, nullptr, result, sizeof(ppg_read_filter_result));
     return PPG_OK;
 }
 
@@ -598,7 +599,7 @@ int ppg_cursor_selected_trim(const ppg_cursor *c, uint32_t **trim) {
 
 int ppg_cursor_trim_result(const ppg_cursor *c, void *result) {
     if (!c || !c->trim || !c->cur || !result) return PPG_ARG_ERROR;
-    readtrim_outputs(&c->cur->sh, nullptr, result);
+    c->cur->sh.trim.outputs(c->cur->sh.n, nullptr, result, sizeof(ppg_read_trim_result));
     return PPG_OK;
 }
 

@@ -142,3 +142,18 @@ struct PpgSelSrc {
 // wave (64 lanes) per kCrcSeg bytes
 constexpr uint32_t kCrcSub = 16384;
 constexpr uint32_t kCrcSeg = 64 * kCrcSub;
+
+// One resident batch as the record-stage launchers take it (ppg_launch.h, from ppg_seqpack.hip on; built
+// by batch_view, ppg_stages.cpp): the batch's output and offset carries, the per-chunk tables at its
+// first chunk, its first record's descriptor and the number of its chunks.
+struct PpgBatchView {
+    const uint8_t *out;
+    const PpgInflateJob *jobs;
+    const PpgInflateResult *res;
+    const uint8_t *offs;
+    const PpgOffsetRef *oref;
+    const PpgParseInfo *info;
+    const uint64_t *base;
+    const uint32_t *recs;
+    int n;
+};

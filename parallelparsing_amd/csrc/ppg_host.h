@@ -1,6 +1,7 @@
 // ppg_host.h — host-side types shared by the translation units of libppgpu.so
-// (ppg_api.cpp: C ABI, index I/O, shards, ingest; ppg_index_gpu.cpp: GPU CreateIndex; ppg_cursor.cpp: record
-// streaming; ppg_chunk.cpp + ppg_find.cpp: per-chunk Decompress; ppg_comm.cpp + ppg_pairs.hip: multi-GPU).
+// (ppg_api.cpp: C ABI, index I/O, shards, ingest; ppg_stages.cpp: the record stages on a resident batch;
+// ppg_index_gpu.cpp: GPU CreateIndex; ppg_cursor.cpp: record streaming; ppg_chunk.cpp + ppg_find.cpp:
+// per-chunk Decompress; ppg_comm.cpp + ppg_pairs.hip: multi-GPU).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <rccl/rccl.h>
@@ -152,6 +153,97 @@ hipError_t grow_buf(B &b, size_t need) {
     return b.alloc(std::max(need, b.n + b.n / 2));
 }
 
+// ---- record stages (ppg_stages.cpp): work on a batch of a shard while its output is resident ----
+// The layout the unit kernels share (ppg_seqpack.hip): a batch's records on 32-base units.
+struct StageLayout {
+    DevBuf<uint64_t> ctot, cbase;   // per-chunk padded bases and their scan (n + 1 entries)
+    PinnedBuf htot;                 // the scan's total, stored by the kernel
+    DevBuf<int64_t> off;            // seq_off / seq_len of the batch's records from carry 0 (shard_layout)
+    DevBuf<uint32_t> len;
+    int64_t total = 0;              // padded bases of the batch laid out last
+};
+
+// What query, filter and trim each carry: the run's accumulators on the device, and what the kernels store
+// to pinned memory, the result struct followed by one count per chunk of the shard.
+struct StageOut {
+    int on = 0;        // attached: every batch of a run goes through the stage
+    int written = 0;   // the last successful run completed it (stages_run_end)
+    DevBuf<uint64_t> acc;
+    PinnedBuf host;
+    int64_t *result() const { return (int64_t *)host.p; }
+    // what the last completed stage left in pinned memory (n: the shard's chunks)
+    void outputs(int32_t n, int64_t *chunk_counts, void *result, size_t result_bytes) const {
+        if (!host.p) {   // a shard without chunks: no batch ran
+            if (result) memset(result, 0, result_bytes);
+            return;
+        }
+        if (result) memcpy(result, host.p, result_bytes);
+        if (chunk_counts && n) memcpy(chunk_counts, host.p + result_bytes, 8 * (size_t)n);
+    }
+};
+
+// ppg_shard_set_seqpack: every batch also packs its reads into these planes (ppg_seqpack.hip), records at
+// their shard record number, bases continuing from the batches before (total)
+struct PackStage {
+    int64_t *off = nullptr;
+    uint32_t *len = nullptr, *bases = nullptr, *mask = nullptr;
+    uint8_t *qual = nullptr;
+    int64_t rec_cap = 0, base_cap = 0;
+    int64_t total = 0;   // padded bases of the run's batches so far
+    int written = 0;     // the last successful run filled the planes
+};
+
+// ppg_shard_set_seqquery: every batch is also searched for pat and its bases counted (ppg_seqquery.hip);
+// hit bits at the shard record number in mask.  acc: records, hits, (unused), count[5].
+struct QueryStage : StageOut {
+    PpgSeqPattern pat = {};
+    int32_t m = 0;
+    uint32_t *mask = nullptr;
+    int64_t rec_cap = 0;
+    DevBuf<uint32_t> bits;   // a batch's hit bits when the caller gives no mask
+};
+
+// ppg_shard_set_readfilter: every batch's records are also measured and filtered (ppg_readfilter.hip);
+// pass bits and metrics rows at the shard record number.  acc: kRfAcc values.
+struct FilterStage : StageOut {
+    PpgReadFilter flt = {};
+    uint32_t *mask = nullptr;
+    int64_t rec_cap = 0;
+    uint8_t *metrics = nullptr;
+    int64_t metrics_cap = 0;
+    int hist = kRfHistRuns;   // ppg_rf_measure's histogram variant (tools/readfilter_probe.py times both)
+    DevBuf<uint64_t> rsc;     // scratch: other | low << 32 and qsum of one batch's records
+};
+
+// ppg_shard_set_readtrim: every batch's records are also trimmed (ppg_readtrim.hip); keep bits and
+// (start, len) rows at the shard record number.  acc: kRtAcc values.
+struct TrimStage : StageOut {
+    PpgReadTrim trm = {};
+    uint32_t *mask = nullptr;
+    int64_t rec_cap = 0;
+    uint32_t *rows = nullptr;
+    int64_t rows_cap = 0;
+    DevBuf<uint32_t> rsc;   // scratch: four planes (lead, win, adapt, trail) of one batch's records
+};
+
+// ppg_shard_set_select: every batch's selected records are also appended to these buffers
+// (ppg_seqselect.hip), output records and bytes continuing from the batches before
+struct SelectStage {
+    int on = 0;
+    int written = 0;   // the last successful run completed the selection
+    const uint32_t *mask = nullptr;
+    int64_t mask_cap = 0;
+    int64_t *recno = nullptr, *off = nullptr;
+    uint32_t *desc = nullptr;
+    uint8_t *bytes = nullptr;
+    int64_t cap = 0, byte_cap = 0;
+    int64_t records = 0, nbytes = 0;   // selected by the run's batches so far
+    DevBuf<uint64_t> ccnt, cbase;      // per chunk: selected records, then their bytes; the scans of both
+    DevBuf<PpgSelSrc> src;             // scratch: where the bytes of a batch's selected records come from
+    DevBuf<int64_t> span;              // scratch: ppg_sel_place's span_first
+    PinnedBuf host;                    // a batch's totals (records, bytes), stored by the kernel
+};
+
 // DecompressAll state over chunks [first, first+n) of an index (ppg_api.cpp); the cursor
 // (ppg_cursor.cpp), the per-chunk Decompress (ppg_chunk.cpp) and the pair check (ppg_pairs.hip)
 // drive it through the functions below.
@@ -191,70 +283,14 @@ struct ppg_shard {
     // ppg_shard_set_keys: every batch also writes its records' spot keys here (global record number)
     int64_t *keys_dev = nullptr;
     int64_t keys_cap = 0;
-    int keys_written = 0;   // the last successful run filled keys_dev (set by shard_run)
-    // ppg_shard_set_seqpack: every batch also packs its reads into these planes (ppg_seqpack.hip),
-    // records at their shard record number, bases continuing from the batches before (sp_total)
-    int64_t *sp_off = nullptr;
-    uint32_t *sp_len = nullptr, *sp_bases = nullptr, *sp_mask = nullptr;
-    uint8_t *sp_qual = nullptr;
-    int64_t sp_rec_cap = 0, sp_base_cap = 0;
-    int64_t sp_total = 0;   // padded bases of the run's batches so far
-    int sp_written = 0;     // the last successful run filled the planes (set by shard_run)
-    DevBuf<uint64_t> sp_ctot, sp_cbase;   // per-chunk padded bases and their scan (n + 1 entries)
-    PinnedBuf sp_htot;                    // the scan's total, stored by the kernel
-    // ppg_shard_set_seqquery: every batch is also searched for sq_pat and its bases counted
-    // (ppg_seqquery.hip); hit bits at the shard record number in sq_mask, totals carried in sq_acc
-    int sq_on = 0;
-    PpgSeqPattern sq_pat = {};
-    int32_t sq_m = 0;
-    uint32_t *sq_mask = nullptr;
-    int64_t sq_rec_cap = 0;
-    int sq_written = 0;                  // the last successful run completed the query (set by shard_run)
-    DevBuf<int64_t> sq_off;              // scratch: seq_off / seq_len of one batch's records
-    DevBuf<uint32_t> sq_len, sq_bits;    // sq_bits: a batch's hit bits when the caller gives no mask
-    DevBuf<uint64_t> sq_acc;             // records, hits, (unused), count[5] of the run so far
-    PinnedBuf sq_host;                   // a ppg_seq_query_result, then hits per chunk: stored by the kernels
-    int64_t sq_total = 0;                // padded bases of the batch the query laid out last (the filter hook reuses it)
-    // ppg_shard_set_readfilter: every batch's records are also measured and filtered (ppg_readfilter.hip);
-    // pass bits and metrics rows at the shard record number, totals carried in rf_acc
-    int rf_on = 0;
-    PpgReadFilter rf_flt = {};
-    uint32_t *rf_mask = nullptr;
-    int64_t rf_rec_cap = 0;
-    uint8_t *rf_metrics = nullptr;
-    int64_t rf_metrics_cap = 0;
-    int rf_written = 0;                  // the last successful run completed the filter (set by shard_run)
-    int rf_hist = kRfHistRuns;           // ppg_rf_measure's histogram variant (tools/readfilter_probe.py times both)
-    DevBuf<uint64_t> rf_rsc;             // scratch: other | low << 32 and qsum of one batch's records
-    DevBuf<uint64_t> rf_acc;             // kRfAcc accumulators of the run so far
-    PinnedBuf rf_host;                   // a ppg_read_filter_result, then passes per chunk: stored by the kernels
-    // ppg_shard_set_readtrim: every batch's records are also trimmed (ppg_readtrim.hip); keep bits and
-    // (start, len) rows at the shard record number, totals carried in rt_acc
-    int rt_on = 0;
-    PpgReadTrim rt_trm = {};
-    uint32_t *rt_mask = nullptr;
-    int64_t rt_rec_cap = 0;
-    uint32_t *rt_rows = nullptr;
-    int64_t rt_rows_cap = 0;
-    int rt_written = 0;                  // the last successful run completed the trim (set by shard_run)
-    DevBuf<uint32_t> rt_rsc;             // scratch: four planes (lead, win, adapt, trail) of one batch's records
-    DevBuf<uint64_t> rt_acc;             // kRtAcc accumulators of the run so far
-    PinnedBuf rt_host;                   // a ppg_read_trim_result, then keeps per chunk: stored by the kernels
-    // ppg_shard_set_select: every batch's selected records are also appended to these buffers
-    // (ppg_seqselect.hip), output records and bytes continuing from the batches before
-    int sel_on = 0;
-    const uint32_t *sel_mask = nullptr;
-    int64_t sel_mask_cap = 0;
-    int64_t *sel_recno = nullptr, *sel_off = nullptr;
-    uint32_t *sel_desc = nullptr;
-    uint8_t *sel_bytes = nullptr;
-    int64_t sel_cap = 0, sel_byte_cap = 0;
-    int64_t sel_records = 0, sel_nbytes = 0;   // selected by the run's batches so far
-    int sel_written = 0;                       // the last successful run completed the selection (set by shard_run)
-    DevBuf<uint64_t> sel_ccnt, sel_cbase;      // per chunk: selected records, then their bytes; the scans of both
-    DevBuf<PpgSelSrc> sel_src;                 // scratch: where the bytes of a batch's selected records come from
-    DevBuf<int64_t> sel_span;                  // scratch: ppg_sel_place's span_first
-    PinnedBuf sel_host;                        // a batch's totals (records, bytes), stored by the kernel
+    int keys_written = 0;   // the last successful run filled keys_dev (stages_run_end)
+    // the record stages (ppg_stages.cpp), run by shard_batch_hooks on every batch while its output is resident
+    StageLayout lay;
+    PackStage pack;
+    QueryStage query;
+    FilterStage filter;
+    TrimStage trim;
+    SelectStage select;
     // split chunks (ppg_shard_set_split): the inflate launch runs sub-jobs, ppg_split_merge folds
     // them back into per-chunk results and census regions
     int32_t nsub = 0;                            // side points in use (0: one wave per chunk)
@@ -298,40 +334,43 @@ int shard_set_split_impl(ppg_shard *sh, int32_t nsub, const int64_t *bit, const 
 int shard_reserve(ppg_shard *sh, const ppg_index *ix, int32_t first,
                   const std::vector<std::pair<int32_t, int32_t>> &ranges, bool split);
 bool pread_parallel(int fd, uint8_t *dst, int64_t off, int64_t len, int threads);
-// packed reads of chunks [b0, b1) of one resident batch (recs: the batch's first descriptor).
-// layout: per-chunk padded bases, their scan and the batch's total (blocks on the shard's stream);
-// pack: seq_off / seq_len of the batch's records (pointers at its first record; bases from carry)
-// and the planes, queued on the stream after a layout of the same chunks.
+// ---- record stages (ppg_stages.cpp).  [b0, b1): chunks of one resident batch; recs: the batch's first
+// descriptor; rec0: its first record's shard record number; tot: its records.  Everything is queued on the
+// shard's stream; the calls said to block synchronise it. ----
+PpgBatchView batch_view(const ppg_shard *sh, int32_t b0, int32_t b1, const uint32_t *recs);
+// batch_collect's one call: the batch's hooks in the order keys, pack, query, filter, trim, select
+int shard_batch_hooks(ppg_shard *sh, int32_t b0, int32_t b1, int64_t tot);
+// ppg_shard_run's two: no hook's output counts as written during a run; a run that succeeded wrote them all
+void stages_run_begin(ppg_shard *sh);
+void stages_run_end(ppg_shard *sh, bool ok);
+// packed reads.  layout: per-chunk padded bases, their scan and the batch's total (blocks); pack: seq_off /
+// seq_len of the batch's records (pointers at its first record; bases from carry) and the planes, after a
+// layout of the same chunks.
 int shard_seq_reserve(ppg_shard *sh, int64_t nchunks);
 int shard_seq_layout(ppg_shard *sh, int32_t b0, int32_t b1, const uint32_t *recs, int64_t *total);
 int shard_seq_pack(ppg_shard *sh, int32_t b0, int32_t b1, const uint32_t *recs, int64_t carry, int64_t total,
                    int64_t *seq_off, uint32_t *seq_len, uint32_t *bases, uint32_t *mask, uint8_t *qual);
-// sequence query of chunks [b0, b1) of one resident batch (recs: the batch's first descriptor, rec0 its
-// first record's shard record number, tot its records), queued on the shard's stream after a layout
-// of its own (which blocks); first: the run's accumulators start from 0.  The totals so far and the
-// chunks' hits are in sq_host once the stream has drained.
+// The batch laid out for the unit kernels of query, filter and trim: shard_seq_layout (blocks), then seq_off /
+// seq_len from carry 0 into sh->lay.  Made once per batch, before the first of those stages; they read it
+// and never make it.
+int shard_layout(ppg_shard *sh, int32_t b0, int32_t b1, const uint32_t *recs, int64_t tot);
+// sequence query, after shard_layout of the same chunks; first: the run's accumulators start from 0.  The
+// totals so far and the chunks' hits are in query.host once the stream has drained.
 int shard_seq_query(ppg_shard *sh, int32_t b0, int32_t b1, const uint32_t *recs, int64_t rec0, int64_t tot,
                     const PpgSeqPattern &pat, int32_t m, uint32_t *mask, bool first);
 bool seqquery_pattern(const uint8_t *pattern, int32_t m, PpgSeqPattern *pat);
-// read filter of chunks [b0, b1) of one resident batch, with the arguments of shard_seq_query; mask and
-// metrics may be null (metrics: row 0 of the plane).  laid_out: a shard_seq_query of the same chunks has
-// just run, its layout (sp_cbase, sq_off, sq_len, sq_total) is used; else the call lays the batch out
-// itself, which blocks.  The totals so far and the chunks' passes are in rf_host once the stream has drained.
+// read filter, with the arguments of shard_seq_query; mask and metrics may be null (metrics: row 0 of the
+// plane).  The totals so far and the chunks' passes are in filter.host once the stream has drained.
 int shard_read_filter(ppg_shard *sh, int32_t b0, int32_t b1, const uint32_t *recs, int64_t rec0, int64_t tot,
-                      const PpgReadFilter &flt, uint32_t *mask, uint8_t *metrics, bool first, bool laid_out);
-void readfilter_outputs(const ppg_shard *sh, int64_t *chunk_passed, void *result);
-// read trim of chunks [b0, b1) of one resident batch, with the arguments of shard_read_filter; mask and
-// rows may be null (rows: row 0 of the plane, two words per record).  laid_out: a shard_seq_query or a
-// shard_read_filter of the same chunks has just run.  The totals so far and the chunks' keeps are in
-// rt_host once the stream has drained.  readtrim_ok: the rules of ppg_read_trim_check, the struct as the
-// kernels' argument.
+                      const PpgReadFilter &flt, uint32_t *mask, uint8_t *metrics, bool first);
+// read trim, with the arguments of shard_read_filter; mask and rows may be null (rows: row 0 of the plane,
+// two words per record).  The totals so far and the chunks' keeps are in trim.host once the stream has
+// drained.  readtrim_ok: the rules of ppg_read_trim_check, the struct as the kernels' argument.
 int shard_read_trim(ppg_shard *sh, int32_t b0, int32_t b1, const uint32_t *recs, int64_t rec0, int64_t tot,
-                    const PpgReadTrim &trm, uint32_t *mask, uint32_t *rows, bool first, bool laid_out);
-void readtrim_outputs(const ppg_shard *sh, int64_t *chunk_kept, void *result);
+                    const PpgReadTrim &trm, uint32_t *mask, uint32_t *rows, bool first);
 bool readtrim_ok(const void *trim, PpgReadTrim *out);
-// record selection of chunks [b0, b1) of one resident batch (recs: the batch's first descriptor; record j
-// of the batch has bit bit0 + j of mask, a null mask selects all).  sizes: the selected records and their
-// bytes (blocks on the shard's stream).  move: after sizes of the same chunks, queues the selection into
+// record selection (record j of the batch has bit bit0 + j of mask, a null mask selects all).  sizes: the
+// selected records and their bytes (blocks).  move: after sizes of the same chunks, queues the selection into
 // the buffers from output record rec_lo and byte byte_lo on; recno counts from bit0.
 int shard_select_reserve(ppg_shard *sh, int64_t nchunks);
 int shard_select_sizes(ppg_shard *sh, int32_t b0, int32_t b1, const uint32_t *recs, const uint32_t *mask, int64_t bit0,

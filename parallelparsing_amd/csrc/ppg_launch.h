@@ -58,81 +58,65 @@ hipError_t ppg_launch_crc(hipStream_t s, const uint8_t *out, uint64_t n, uint64_
                           uint32_t *seg_raw, uint64_t nseg);
 
 // ---- ppg_seqpack.hip ----
+// From here on the launchers take the batch as a PpgBatchView (ppg_device.h; batch_view, ppg_stages.cpp)
+// and unpack it into their kernel's arguments.
 // Weak: libppgpu.so always links that object, but the host-only sanitizer build (tests/native) links
 // the host translation units with the kernel objects of inflate / parse / index alone; there the
-// packed-read entry points fail with PPG_UNSUPPORTED (seq_linked, ppg_api.cpp) instead of the link
+// packed-read entry points fail with PPG_UNSUPPORTED (seq_linked, ppg_stages.cpp) instead of the link
 // failing.  There is no other implementation to fall back to.  (ppg_seqpack.hip includes this header
 // as well, which makes its definitions weak symbols: they are the only ones, so they link the same.)
 #define PPG_WEAK __attribute__((weak))
-PPG_WEAK hipError_t ppg_launch_seq_totals(hipStream_t s, const PpgInflateResult *ires, const PpgParseInfo *info,
-                                          const uint64_t *base, const uint32_t *recs, uint64_t *ctot, int n);
+PPG_WEAK hipError_t ppg_launch_seq_totals(hipStream_t s, const PpgBatchView &v, uint64_t *ctot);
 PPG_WEAK hipError_t ppg_launch_seq_scan(hipStream_t s, const uint64_t *ctot, uint64_t *cbase, uint64_t *host_total,
                                         int n);
-PPG_WEAK hipError_t ppg_launch_seq_offsets(hipStream_t s, const PpgInflateResult *ires, const PpgParseInfo *info,
-                                           const uint64_t *base, const uint32_t *recs, const uint64_t *cbase,
-                                           int64_t carry, int64_t *seq_off, uint32_t *seq_len, int n);
-PPG_WEAK hipError_t ppg_launch_seq_pack(hipStream_t s, const uint8_t *out, const PpgInflateJob *jobs,
-                                        const PpgInflateResult *ires, const uint8_t *offs, const PpgOffsetRef *oref,
-                                        const PpgParseInfo *info, const uint64_t *base, const uint32_t *recs,
-                                        const uint64_t *cbase, const int64_t *seq_off, const uint32_t *seq_len,
-                                        int64_t carry, uint64_t total, uint32_t *bases, uint32_t *mask, uint8_t *qual,
-                                        int n);
+PPG_WEAK hipError_t ppg_launch_seq_offsets(hipStream_t s, const PpgBatchView &v, const uint64_t *cbase, int64_t carry,
+                                           int64_t *seq_off, uint32_t *seq_len);
+PPG_WEAK hipError_t ppg_launch_seq_pack(hipStream_t s, const PpgBatchView &v, const uint64_t *cbase,
+                                        const int64_t *seq_off, const uint32_t *seq_len, int64_t carry, uint64_t total,
+                                        uint32_t *bases, uint32_t *mask, uint8_t *qual);
 
 // ---- ppg_seqquery.hip ----
-// Weak for the same reason (seqquery_linked, ppg_api.cpp).
-PPG_WEAK hipError_t ppg_launch_seq_query(hipStream_t s, const uint8_t *out, const PpgInflateJob *jobs,
-                                         const uint8_t *offs, const PpgOffsetRef *oref, const PpgParseInfo *info,
-                                         const uint64_t *base, const uint32_t *recs, const uint64_t *cbase,
+// Weak for the same reason (seqquery_linked, ppg_stages.cpp).
+PPG_WEAK hipError_t ppg_launch_seq_query(hipStream_t s, const PpgBatchView &v, const uint64_t *cbase,
                                          const int64_t *seq_off, const uint32_t *seq_len, uint64_t total,
                                          const PpgSeqPattern *pat, int m, uint32_t *hit_words, uint64_t rec0,
-                                         uint64_t *acc, int n);
-PPG_WEAK hipError_t ppg_launch_seq_query_chunks(hipStream_t s, const PpgInflateResult *ires, const PpgParseInfo *info,
-                                                const uint64_t *base, int m, uint32_t *hit_words, uint64_t rec0,
-                                                uint64_t *acc, int64_t *host_chunk_hits, int n);
+                                         uint64_t *acc);
+PPG_WEAK hipError_t ppg_launch_seq_query_chunks(hipStream_t s, const PpgBatchView &v, int m, uint32_t *hit_words,
+                                                uint64_t rec0, uint64_t *acc, int64_t *host_chunk_hits);
 PPG_WEAK hipError_t ppg_launch_seq_query_totals(hipStream_t s, const uint64_t *acc, int64_t *host_result);
 
 // ---- ppg_readfilter.hip ----
-// Weak for the same reason (readfilter_linked, ppg_api.cpp).
-PPG_WEAK hipError_t ppg_launch_rf_measure(hipStream_t s, const uint8_t *out, const PpgInflateJob *jobs,
-                                          const uint8_t *offs, const PpgOffsetRef *oref, const PpgParseInfo *info,
-                                          const uint64_t *base, const uint32_t *recs, const uint64_t *cbase,
+// Weak for the same reason (readfilter_linked, ppg_stages.cpp).
+PPG_WEAK hipError_t ppg_launch_rf_measure(hipStream_t s, const PpgBatchView &v, const uint64_t *cbase,
                                           const int64_t *seq_off, const uint32_t *seq_len, uint64_t total, uint32_t thr,
-                                          uint64_t *rsc, uint64_t *acc, int n, int hist);
-PPG_WEAK hipError_t ppg_launch_rf_decide(hipStream_t s, const uint8_t *out, const PpgInflateJob *jobs,
-                                         const PpgInflateResult *ires, const uint8_t *offs, const PpgOffsetRef *oref,
-                                         const PpgParseInfo *info, const uint64_t *base, const uint32_t *recs,
-                                         const uint64_t *rsc, const PpgReadFilter *f, uint32_t *words, uint64_t rec0,
-                                         uint8_t *metrics, uint64_t *acc, int64_t *host_chunk_passed, int n);
+                                          uint64_t *rsc, uint64_t *acc, int hist);
+PPG_WEAK hipError_t ppg_launch_rf_decide(hipStream_t s, const PpgBatchView &v, const uint64_t *rsc,
+                                         const PpgReadFilter *f, uint32_t *words, uint64_t rec0, uint8_t *metrics,
+                                         uint64_t *acc, int64_t *host_chunk_passed);
 PPG_WEAK hipError_t ppg_launch_rf_totals(hipStream_t s, const uint64_t *acc, int64_t *host_result);
 
 // ---- ppg_readtrim.hip ----
-// Weak for the same reason (readtrim_linked, ppg_api.cpp).
-PPG_WEAK hipError_t ppg_launch_rt_measure(hipStream_t s, const uint8_t *out, const PpgInflateJob *jobs,
-                                          const uint8_t *offs, const PpgOffsetRef *oref, const PpgParseInfo *info,
-                                          const uint64_t *base, const uint32_t *recs, const uint64_t *cbase,
+// Weak for the same reason (readtrim_linked, ppg_stages.cpp).
+PPG_WEAK hipError_t ppg_launch_rt_measure(hipStream_t s, const PpgBatchView &v, const uint64_t *cbase,
                                           const int64_t *seq_off, const uint32_t *seq_len, uint64_t total,
-                                          const PpgReadTrim *tr, uint32_t *rsc, uint64_t tot, int n);
-PPG_WEAK hipError_t ppg_launch_rt_decide(hipStream_t s, const PpgInflateResult *ires, const PpgParseInfo *info,
-                                         const uint64_t *base, const uint32_t *recs, const uint32_t *rsc, uint64_t tot,
+                                          const PpgReadTrim *tr, uint32_t *rsc, uint64_t tot);
+PPG_WEAK hipError_t ppg_launch_rt_decide(hipStream_t s, const PpgBatchView &v, const uint32_t *rsc, uint64_t tot,
                                          const PpgReadTrim *tr, uint32_t *words, uint64_t rec0, uint32_t *trim,
-                                         uint64_t *acc, int64_t *host_chunk_kept, int n);
+                                         uint64_t *acc, int64_t *host_chunk_kept);
 PPG_WEAK hipError_t ppg_launch_rt_totals(hipStream_t s, const uint64_t *acc, int64_t *host_result);
 PPG_WEAK hipError_t ppg_launch_rt_gather(hipStream_t s, const uint32_t *trim, const int64_t *recno, int64_t rec0,
                                          uint64_t n, uint32_t *dst);
 
 // ---- ppg_seqselect.hip ----
-// Weak for the same reason (select_linked, ppg_api.cpp).
-PPG_WEAK hipError_t ppg_launch_sel_count(hipStream_t s, const PpgInflateResult *ires, const PpgParseInfo *info,
-                                         const uint64_t *base, const uint32_t *recs, const uint32_t *mask,
-                                         uint64_t bit0, uint64_t *crec, uint64_t *cbyte, int n);
+// Weak for the same reason (select_linked, ppg_stages.cpp).
+PPG_WEAK hipError_t ppg_launch_sel_count(hipStream_t s, const PpgBatchView &v, const uint32_t *mask, uint64_t bit0,
+                                         uint64_t *crec, uint64_t *cbyte);
 PPG_WEAK hipError_t ppg_launch_sel_scan(hipStream_t s, const uint64_t *crec, const uint64_t *cbyte, uint64_t *rbase,
                                         uint64_t *bbase, int64_t *host_totals, int n);
-PPG_WEAK hipError_t ppg_launch_sel_place(hipStream_t s, const PpgInflateResult *ires, const PpgParseInfo *info,
-                                         const uint64_t *base, const uint32_t *recs, const uint32_t *mask,
-                                         uint64_t bit0, const uint64_t *rbase, const uint64_t *bbase, const uint8_t *out,
-                                         const PpgInflateJob *jobs, const uint8_t *offs, const PpgOffsetRef *oref,
-                                         int64_t rec_lo, int64_t byte_lo, int64_t *recno, int64_t *sel_off, uint32_t *desc,
-                                         PpgSelSrc *src, int64_t *span_first, int n);
+PPG_WEAK hipError_t ppg_launch_sel_place(hipStream_t s, const PpgBatchView &v, const uint32_t *mask, uint64_t bit0,
+                                         const uint64_t *rbase, const uint64_t *bbase, int64_t rec_lo, int64_t byte_lo,
+                                         int64_t *recno, int64_t *sel_off, uint32_t *desc, PpgSelSrc *src,
+                                         int64_t *span_first);
 PPG_WEAK hipError_t ppg_launch_sel_copy(hipStream_t s, const int64_t *sel_off, const PpgSelSrc *src,
                                         const int64_t *span_first, int64_t rec_lo, int64_t rec_hi, int64_t d0, int64_t d1,
                                         uint8_t *dst);

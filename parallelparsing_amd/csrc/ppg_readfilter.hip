@@ -8,9 +8,9 @@
 //
 //   layout   as the packed reads and the queries: P_j = 32 * ceil(L_j / 32) per record, per-chunk sums,
 //            their scan, seq_off / seq_len per record (ppg_seq_totals, ppg_seq_scan, ppg_seq_offsets,
-//            unchanged; a batch the query hook has just laid out is not laid out again).
-//   measure  one thread per 32-base unit (ppg_rf_measure), chunk and record by the two binary searches
-//            of ppg_seq_query.  The unit reads its <= 32 bytes of S_j and the bytes of Q_j at the same
+//            unchanged; made once per batch for the query, the filter and the trim: shard_layout).
+//   measure  one thread per 32-base unit (ppg_rf_measure), chunk and record by unit_lookup
+//            (ppg_seqload.h).  The unit reads its <= 32 bytes of S_j and the bytes of Q_j at the same
 //            indices.  Consecutive lanes belong to the same or to successive records, so the per-lane
 //            (other, low, qsum) are summed within the wave segmented by record (a Hillis-Steele scan
 //            whose step adds the lane `o` below only when it has the same record), and the last lane
@@ -45,21 +45,6 @@
 #include "ppg_launch.h"
 #include "ppg_seqload.h"
 
-namespace {
-
-// 1 for 'A' 'C' 'G' 'T': the byte is 0x40..0x5F and its low five bits are 1, 3, 7 or 20
-__device__ __forceinline__ uint32_t is_acgt(uint32_t c) {
-    return (c >> 5) == 2u ? (0x0010008Au >> (c & 31u)) & 1u : 0u;
-}
-
-__device__ __forceinline__ unsigned long long wave_sum64(unsigned long long v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
-    return v;   // lane 0 holds the sum
-}
-
-}  // namespace
-
 // One thread per 32-base unit of the batch.  seq_off / seq_len / recs / rsc point at the batch's first
 // record; cbase, seq_off are batch-relative (carry 0).  Record j of the batch gets rsc[2 j] += other |
 // low << 32 and rsc[2 j + 1] += qsum over the indices [0, P_j) of S_j and Q_j; acc[9 + v] += Quality
@@ -81,18 +66,9 @@ __global__ __launch_bounds__(256) void ppg_rf_measure(
     const uint64_t u = (uint64_t)blockIdx.x * 256 + t;
     if (u < units) {
         const uint64_t rel = 32 * u;
-        int lo = 0, hi = nchunks;                    // invariant: cbase[lo] <= rel < cbase[hi]
-        while (hi - lo > 1) {
-            const int mid = (lo + hi) >> 1;
-            if (cbase[mid] <= rel) lo = mid; else hi = mid;
-        }
-        const int k = lo;
-        uint64_t jl = base[k], jh = jl + info[k].records;   // seq_off[jl] <= rel < seq_off[jh]
-        while (jh - jl > 1) {
-            const uint64_t mid = (jl + jh) >> 1;
-            if (seq_off[mid] <= (int64_t)rel) jl = mid; else jh = mid;
-        }
-        const uint64_t j = jl;
+        int k;
+        uint64_t j;
+        unit_lookup(cbase, base, info, seq_off, nchunks, rel, 0, k, j);
         jkey = j;
         const uint32_t i0 = (uint32_t)((int64_t)rel - seq_off[j]);   // the unit's first index within the record
         const uint32_t L = seq_len[j];
@@ -269,36 +245,34 @@ extern "C" __global__ __launch_bounds__(256) void ppg_rf_totals(const unsigned l
 }
 
 // ------------------------------------------------------------------------------------------
-// launchers (ppg_api.cpp)
+// launchers (ppg_stages.cpp); v: the batch (ppg_device.h)
 // ------------------------------------------------------------------------------------------
-// total: the batch's padded bases (ppg_seq_scan); pointers at the batch's first chunk / record
-hipError_t ppg_launch_rf_measure(hipStream_t s, const uint8_t *out, const PpgInflateJob *jobs, const uint8_t *offs,
-                                 const PpgOffsetRef *oref, const PpgParseInfo *info, const uint64_t *base,
-                                 const uint32_t *recs, const uint64_t *cbase, const int64_t *seq_off,
-                                 const uint32_t *seq_len, uint64_t total, uint32_t thr, uint64_t *rsc, uint64_t *acc, int n,
+// total: the batch's padded bases (ppg_seq_scan)
+hipError_t ppg_launch_rf_measure(hipStream_t s, const PpgBatchView &v, const uint64_t *cbase, const int64_t *seq_off,
+                                 const uint32_t *seq_len, uint64_t total, uint32_t thr, uint64_t *rsc, uint64_t *acc,
                                  int hist) {
     const uint64_t units = total / 32;
-    if (n <= 0 || units == 0) return hipSuccess;
+    if (v.n <= 0 || units == 0) return hipSuccess;
     const dim3 grid((unsigned)((units + 255) / 256));
     if (hist == kRfHistBytes)
-        hipLaunchKernelGGL(ppg_rf_measure<kRfHistBytes>, grid, dim3(256), 0, s, out, jobs, offs, oref, info, base, recs, cbase,
-                           seq_off, seq_len, units, thr, (unsigned long long *)rsc, (unsigned long long *)acc, n);
+        hipLaunchKernelGGL(ppg_rf_measure<kRfHistBytes>, grid, dim3(256), 0, s, v.out, v.jobs, v.offs, v.oref, v.info, v.base,
+                           v.recs, cbase, seq_off, seq_len, units, thr, (unsigned long long *)rsc, (unsigned long long *)acc,
+                           v.n);
     else
-        hipLaunchKernelGGL(ppg_rf_measure<kRfHistRuns>, grid, dim3(256), 0, s, out, jobs, offs, oref, info, base, recs, cbase,
-                           seq_off, seq_len, units, thr, (unsigned long long *)rsc, (unsigned long long *)acc, n);
+        hipLaunchKernelGGL(ppg_rf_measure<kRfHistRuns>, grid, dim3(256), 0, s, v.out, v.jobs, v.offs, v.oref, v.info, v.base,
+                           v.recs, cbase, seq_off, seq_len, units, thr, (unsigned long long *)rsc, (unsigned long long *)acc,
+                           v.n);
     return hipGetLastError();
 }
 
 // metrics: row 0 of the plane (the batch's rows start at rec0); words: the mask's word 0
-hipError_t ppg_launch_rf_decide(hipStream_t s, const uint8_t *out, const PpgInflateJob *jobs, const PpgInflateResult *ires,
-                                const uint8_t *offs, const PpgOffsetRef *oref, const PpgParseInfo *info,
-                                const uint64_t *base, const uint32_t *recs, const uint64_t *rsc, const PpgReadFilter *f,
-                                uint32_t *words, uint64_t rec0, uint8_t *metrics, uint64_t *acc, int64_t *host_chunk_passed,
-                                int n) {
-    if (n <= 0) return hipSuccess;
-    hipLaunchKernelGGL(ppg_rf_decide, dim3(n), dim3(256), 0, s, out, jobs, ires, offs, oref, info, base, recs,
-                       (const unsigned long long *)rsc, *f, words, rec0, metrics, (unsigned long long *)acc,
-                       host_chunk_passed, n);
+hipError_t ppg_launch_rf_decide(hipStream_t s, const PpgBatchView &v, const uint64_t *rsc, const PpgReadFilter *f,
+                                uint32_t *words, uint64_t rec0, uint8_t *metrics, uint64_t *acc,
+                                int64_t *host_chunk_passed) {
+    if (v.n <= 0) return hipSuccess;
+    hipLaunchKernelGGL(ppg_rf_decide, dim3(v.n), dim3(256), 0, s, v.out, v.jobs, v.res, v.offs, v.oref, v.info, v.base,
+                       v.recs, (const unsigned long long *)rsc, *f, words, rec0, metrics, (unsigned long long *)acc,
+                       host_chunk_passed, v.n);
     return hipGetLastError();
 }
 

@@ -5,10 +5,10 @@
 // host; here the window is made where the text already is, and the selection (ppg_seqselect.hip) hands
 // out the records with 8 more bytes each.  No text is rebuilt.
 //
-//   layout   the pack's, unchanged (ppg_seq_totals, ppg_seq_scan, ppg_seq_offsets); a batch the query or
-//            the filter hook has just laid out is not laid out again.
-//   measure  one thread per 32-base unit (ppg_rt_measure), chunk and record by the two binary searches
-//            of ppg_seq_query.  Every cut is decided on [b0, e0) on its own, so a unit gives four
+//   layout   the pack's, unchanged (ppg_seq_totals, ppg_seq_scan, ppg_seq_offsets), made once per batch for
+//            the query, the filter and the trim (shard_layout, ppg_stages.cpp).
+//   measure  one thread per 32-base unit (ppg_rt_measure), chunk and record by unit_lookup
+//            (ppg_seqload.h).  Every cut is decided on [b0, e0) on its own, so a unit gives four
 //            candidates among the positions it owns: the least index at or above the leading threshold,
 //            1 + the greatest at or above the trailing one, the least start of a failing full window and
 //            the least adapter start.  A window or an adapter match belongs to the unit that owns its
@@ -51,12 +51,6 @@ namespace {
 
 constexpr uint32_t kNone = 0xFFFFFFFFu;   // a minimum nobody has found
 
-__device__ __forceinline__ unsigned long long wave_sum64(unsigned long long v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
-    return v;   // lane 0 holds the sum
-}
-
 // the number of non-zero bytes of w
 __device__ __forceinline__ uint32_t nonzero_bytes(uint32_t w) {
     return (uint32_t)__popc((((w & 0x7F7F7F7Fu) + 0x7F7F7F7Fu) | w) & 0x80808080u);
@@ -89,18 +83,9 @@ __global__ __launch_bounds__(256) void ppg_rt_measure(
     const uint64_t u = (uint64_t)blockIdx.x * 256 + t;
     if (u < units) {
         const uint64_t rel = 32 * u;
-        int lo = 0, hi = nchunks;                    // invariant: cbase[lo] <= rel < cbase[hi]
-        while (hi - lo > 1) {
-            const int mid = (lo + hi) >> 1;
-            if (cbase[mid] <= rel) lo = mid; else hi = mid;
-        }
-        const int k = lo;
-        uint64_t jl = base[k], jh = jl + info[k].records;   // seq_off[jl] <= rel < seq_off[jh]
-        while (jh - jl > 1) {
-            const uint64_t mid = (jl + jh) >> 1;
-            if (seq_off[mid] <= (int64_t)rel) jl = mid; else jh = mid;
-        }
-        const uint64_t j = jl;
+        int k;
+        uint64_t j;
+        unit_lookup(cbase, base, info, seq_off, nchunks, rel, 0, k, j);
         jkey = j;
         const int64_t i0 = (int64_t)rel - seq_off[j];   // the unit's first index within the record
         const int64_t L = seq_len[j];
@@ -326,35 +311,32 @@ extern "C" __global__ __launch_bounds__(256) void ppg_rt_gather(const uint2 *__r
 }
 
 // ------------------------------------------------------------------------------------------
-// launchers (ppg_api.cpp, ppg_cursor.cpp)
+// launchers (ppg_stages.cpp, ppg_cursor.cpp); v: the batch (ppg_device.h)
 // ------------------------------------------------------------------------------------------
-// total: the batch's padded bases (ppg_seq_scan); pointers at the batch's first chunk / record; rsc: four
-// planes of tot words, initialised by the caller (three of all ones, then one of zeros)
-hipError_t ppg_launch_rt_measure(hipStream_t s, const uint8_t *out, const PpgInflateJob *jobs, const uint8_t *offs,
-                                 const PpgOffsetRef *oref, const PpgParseInfo *info, const uint64_t *base,
-                                 const uint32_t *recs, const uint64_t *cbase, const int64_t *seq_off,
-                                 const uint32_t *seq_len, uint64_t total, const PpgReadTrim *tr, uint32_t *rsc, uint64_t tot,
-                                 int n) {
+// total: the batch's padded bases (ppg_seq_scan); rsc: four planes of tot words, initialised by the caller
+// (three of all ones, then one of zeros)
+hipError_t ppg_launch_rt_measure(hipStream_t s, const PpgBatchView &v, const uint64_t *cbase, const int64_t *seq_off,
+                                 const uint32_t *seq_len, uint64_t total, const PpgReadTrim *tr, uint32_t *rsc,
+                                 uint64_t tot) {
     const uint64_t units = total / 32;
-    if (n <= 0 || units == 0 || !(tr->ops & 15)) return hipSuccess;   // (no cut looks at a byte)
+    if (v.n <= 0 || units == 0 || !(tr->ops & 15)) return hipSuccess;   // (no cut looks at a byte)
     const dim3 grid((unsigned)((units + 255) / 256));
     if (tr->ops & 8)
-        hipLaunchKernelGGL(ppg_rt_measure<true>, grid, dim3(256), 0, s, out, jobs, offs, oref, info, base, recs, cbase,
-                           seq_off, seq_len, units, *tr, rsc, tot, n);
+        hipLaunchKernelGGL(ppg_rt_measure<true>, grid, dim3(256), 0, s, v.out, v.jobs, v.offs, v.oref, v.info, v.base, v.recs,
+                           cbase, seq_off, seq_len, units, *tr, rsc, tot, v.n);
     else
-        hipLaunchKernelGGL(ppg_rt_measure<false>, grid, dim3(256), 0, s, out, jobs, offs, oref, info, base, recs, cbase,
-                           seq_off, seq_len, units, *tr, rsc, tot, n);
+        hipLaunchKernelGGL(ppg_rt_measure<false>, grid, dim3(256), 0, s, v.out, v.jobs, v.offs, v.oref, v.info, v.base, v.recs,
+                           cbase, seq_off, seq_len, units, *tr, rsc, tot, v.n);
     return hipGetLastError();
 }
 
 // trim: row 0 of the plane (the batch's rows start at rec0); words: the mask's word 0
-hipError_t ppg_launch_rt_decide(hipStream_t s, const PpgInflateResult *ires, const PpgParseInfo *info, const uint64_t *base,
-                                const uint32_t *recs, const uint32_t *rsc, uint64_t tot, const PpgReadTrim *tr,
-                                uint32_t *words, uint64_t rec0, uint32_t *trim, uint64_t *acc, int64_t *host_chunk_kept,
-                                int n) {
-    if (n <= 0) return hipSuccess;
-    hipLaunchKernelGGL(ppg_rt_decide, dim3(n), dim3(256), 0, s, ires, info, base, recs, rsc, tot, *tr, words, rec0, trim,
-                       (unsigned long long *)acc, host_chunk_kept, n);
+hipError_t ppg_launch_rt_decide(hipStream_t s, const PpgBatchView &v, const uint32_t *rsc, uint64_t tot,
+                                const PpgReadTrim *tr, uint32_t *words, uint64_t rec0, uint32_t *trim, uint64_t *acc,
+                                int64_t *host_chunk_kept) {
+    if (v.n <= 0) return hipSuccess;
+    hipLaunchKernelGGL(ppg_rt_decide, dim3(v.n), dim3(256), 0, s, v.res, v.info, v.base, v.recs, rsc, tot, *tr, words, rec0,
+                       trim, (unsigned long long *)acc, host_chunk_kept, v.n);
     return hipGetLastError();
 }
 

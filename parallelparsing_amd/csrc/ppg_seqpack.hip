@@ -12,8 +12,8 @@
 //            a carried base (ppg_seq_offsets: a block per chunk, 256-record tiles scanned in LDS).
 //   pack     one thread per 32-base output unit (ppg_seq_pack), not per record: reads of 36 to
 //            2,000 bases would leave most lanes of a per-record mapping idle.  The unit's chunk and
-//            record come from two binary searches (chunk bases, then the chunk's slice of seq_off;
-//            both tables are small and stay in L2).  The unit's 32 source bytes are 9 aligned
+//            record come from two binary searches (unit_lookup, ppg_seqload.h: chunk bases, then the
+//            chunk's slice of seq_off; both tables are small and stay in L2).  The unit's 32 source bytes are 9 aligned
 //            dwords + v_alignbyte, as ppg_pack_raw loads them (the output buffer has a 64-byte
 //            tail); a unit that touches offset_k goes bytewise through offs / oref.  Each thread
 //            stores one uint2 of bases, one mask word and two uint4 of qualities, so a wave writes
@@ -43,11 +43,6 @@ __device__ __forceinline__ uint32_t seq_len_of(const uint32_t *r, bool ok) {
     return ok && n2 > n1 ? n2 - n1 - 1 : 0u;
 }
 __device__ __forceinline__ uint64_t pad32(uint32_t L) { return ((uint64_t)L + 31) & ~(uint64_t)31; }
-
-// 1 for 'A' 'C' 'G' 'T': the byte is 0x40..0x5F and its low five bits are 1, 3, 7 or 20
-__device__ __forceinline__ uint32_t is_acgt(uint32_t c) {
-    return (c >> 5) == 2u ? (0x0010008Au >> (c & 31u)) & 1u : 0u;
-}
 
 }  // namespace
 
@@ -149,21 +144,10 @@ extern "C" __global__ __launch_bounds__(256) void ppg_seq_pack(
     const uint64_t u = (uint64_t)blockIdx.x * 256 + threadIdx.x;
     if (u >= units) return;
     const uint64_t rel = 32 * u;                 // batch-relative base position
-    // chunk: the last k with cbase[k] <= rel (chunks without bases share their successor's base)
-    int lo = 0, hi = nchunks;                    // invariant: cbase[lo] <= rel < cbase[hi]
-    while (hi - lo > 1) {
-        const int mid = (lo + hi) >> 1;
-        if (cbase[mid] <= rel) lo = mid; else hi = mid;
-    }
-    const int k = lo;
-    // record: the last j of the chunk with seq_off[j] <= b (records without bases likewise)
+    int k;
+    uint64_t j;
+    unit_lookup(cbase, base, info, seq_off, nchunks, rel, carry, k, j);
     const int64_t b = carry + (int64_t)rel;
-    uint64_t jl = base[k], jh = jl + info[k].records;   // seq_off[jl] <= b < seq_off[jh]
-    while (jh - jl > 1) {
-        const uint64_t mid = (jl + jh) >> 1;
-        if (seq_off[mid] <= b) jl = mid; else jh = mid;
-    }
-    const uint64_t j = jl;
     const uint32_t i0 = (uint32_t)(b - seq_off[j]);     // first base of the unit within the record
     const uint32_t L = seq_len[j];
     const uint32_t n1 = recs[4 * j], n3 = recs[4 * j + 2], n4 = recs[4 * j + 3];
@@ -200,14 +184,12 @@ extern "C" __global__ __launch_bounds__(256) void ppg_seq_pack(
 }
 
 // ------------------------------------------------------------------------------------------
-// launchers (ppg_api.cpp, ppg_cursor.cpp)
+// launchers (ppg_stages.cpp); v: the batch (ppg_device.h)
 // ------------------------------------------------------------------------------------------
-// per-chunk padded totals of chunks [0, n) (pointers at the first of them; recs at their batch's
-// first record) into ctot
-hipError_t ppg_launch_seq_totals(hipStream_t s, const PpgInflateResult *ires, const PpgParseInfo *info,
-                                 const uint64_t *base, const uint32_t *recs, uint64_t *ctot, int n) {
-    if (n <= 0) return hipSuccess;
-    hipLaunchKernelGGL(ppg_seq_totals, dim3(n), dim3(256), 0, s, ires, info, base, recs, ctot, n);
+// per-chunk padded totals of the batch's chunks into ctot
+hipError_t ppg_launch_seq_totals(hipStream_t s, const PpgBatchView &v, uint64_t *ctot) {
+    if (v.n <= 0) return hipSuccess;
+    hipLaunchKernelGGL(ppg_seq_totals, dim3(v.n), dim3(256), 0, s, v.res, v.info, v.base, v.recs, ctot, v.n);
     return hipGetLastError();
 }
 
@@ -217,23 +199,21 @@ hipError_t ppg_launch_seq_scan(hipStream_t s, const uint64_t *ctot, uint64_t *cb
     return hipGetLastError();
 }
 
-hipError_t ppg_launch_seq_offsets(hipStream_t s, const PpgInflateResult *ires, const PpgParseInfo *info,
-                                  const uint64_t *base, const uint32_t *recs, const uint64_t *cbase, int64_t carry,
-                                  int64_t *seq_off, uint32_t *seq_len, int n) {
-    if (n <= 0) return hipSuccess;
-    hipLaunchKernelGGL(ppg_seq_offsets, dim3(n), dim3(256), 0, s, ires, info, base, recs, cbase, carry, seq_off, seq_len, n);
+hipError_t ppg_launch_seq_offsets(hipStream_t s, const PpgBatchView &v, const uint64_t *cbase, int64_t carry,
+                                  int64_t *seq_off, uint32_t *seq_len) {
+    if (v.n <= 0) return hipSuccess;
+    hipLaunchKernelGGL(ppg_seq_offsets, dim3(v.n), dim3(256), 0, s, v.res, v.info, v.base, v.recs, cbase, carry, seq_off,
+                       seq_len, v.n);
     return hipGetLastError();
 }
 
 // total: the batch's padded bases (a multiple of 32)
-hipError_t ppg_launch_seq_pack(hipStream_t s, const uint8_t *out, const PpgInflateJob *jobs, const PpgInflateResult *ires,
-                               const uint8_t *offs, const PpgOffsetRef *oref, const PpgParseInfo *info,
-                               const uint64_t *base, const uint32_t *recs, const uint64_t *cbase, const int64_t *seq_off,
+hipError_t ppg_launch_seq_pack(hipStream_t s, const PpgBatchView &v, const uint64_t *cbase, const int64_t *seq_off,
                                const uint32_t *seq_len, int64_t carry, uint64_t total, uint32_t *bases, uint32_t *mask,
-                               uint8_t *qual, int n) {
+                               uint8_t *qual) {
     const uint64_t units = total / 32;
-    if (n <= 0 || units == 0) return hipSuccess;
-    hipLaunchKernelGGL(ppg_seq_pack, dim3((unsigned)((units + 255) / 256)), dim3(256), 0, s, out, jobs, ires, offs, oref,
-                       info, base, recs, cbase, seq_off, seq_len, carry, units, bases, mask, qual, n);
+    if (v.n <= 0 || units == 0) return hipSuccess;
+    hipLaunchKernelGGL(ppg_seq_pack, dim3((unsigned)((units + 255) / 256)), dim3(256), 0, s, v.out, v.jobs, v.res, v.offs,
+                       v.oref, v.info, v.base, v.recs, cbase, seq_off, seq_len, carry, units, bases, mask, qual, v.n);
     return hipGetLastError();
 }

@@ -10,7 +10,7 @@
 //            scan, then seq_off / seq_len per record into shard scratch (ppg_seq_totals, ppg_seq_scan,
 //            ppg_seq_offsets, unchanged).
 //   query    one thread per 32-base unit (ppg_seq_query): chunk and record by the two binary searches of
-//            ppg_seq_pack.  The unit counts its own <= 32 bytes and tests the pattern starts it owns,
+//            ppg_seq_pack (unit_lookup, ppg_seqload.h).  The unit counts its own <= 32 bytes and tests the pattern starts it owns,
 //            [i0, i0 + 32) n [0, L - m], reading at most 32 + m - 1 bytes of the Sequence and nothing
 //            outside it: a match that straddles units is found by exactly the unit that owns its start.
 //            The match is shift-and (bitap) with the state in one 64-bit register (m <= 64) and the
@@ -77,18 +77,9 @@ extern "C" __global__ __launch_bounds__(256) void ppg_seq_query(
     const uint64_t u = (uint64_t)blockIdx.x * 256 + t;
     if (u < units) {
         const uint64_t rel = 32 * u;
-        int lo = 0, hi = nchunks;                    // invariant: cbase[lo] <= rel < cbase[hi]
-        while (hi - lo > 1) {
-            const int mid = (lo + hi) >> 1;
-            if (cbase[mid] <= rel) lo = mid; else hi = mid;
-        }
-        const int k = lo;
-        uint64_t jl = base[k], jh = jl + info[k].records;   // seq_off[jl] <= rel < seq_off[jh]
-        while (jh - jl > 1) {
-            const uint64_t mid = (jl + jh) >> 1;
-            if (seq_off[mid] <= (int64_t)rel) jl = mid; else jh = mid;
-        }
-        const uint64_t j = jl;
+        int k;
+        uint64_t j;
+        unit_lookup(cbase, base, info, seq_off, nchunks, rel, 0, k, j);
         const uint32_t i0 = (uint32_t)((int64_t)rel - seq_off[j]);   // the unit's first base within the record
         const uint32_t L = seq_len[j];
         const uint32_t n1 = recs[4 * j];
@@ -185,27 +176,25 @@ extern "C" __global__ __launch_bounds__(64) void ppg_seq_query_totals(const unsi
 }
 
 // ------------------------------------------------------------------------------------------
-// launchers (ppg_api.cpp)
+// launchers (ppg_stages.cpp); v: the batch (ppg_device.h)
 // ------------------------------------------------------------------------------------------
-// total: the batch's padded bases (ppg_seq_scan); pointers at the batch's first chunk / record
-hipError_t ppg_launch_seq_query(hipStream_t s, const uint8_t *out, const PpgInflateJob *jobs, const uint8_t *offs,
-                                const PpgOffsetRef *oref, const PpgParseInfo *info, const uint64_t *base,
-                                const uint32_t *recs, const uint64_t *cbase, const int64_t *seq_off,
+// total: the batch's padded bases (ppg_seq_scan)
+hipError_t ppg_launch_seq_query(hipStream_t s, const PpgBatchView &v, const uint64_t *cbase, const int64_t *seq_off,
                                 const uint32_t *seq_len, uint64_t total, const PpgSeqPattern *pat, int m,
-                                uint32_t *hit_words, uint64_t rec0, uint64_t *acc, int n) {
+                                uint32_t *hit_words, uint64_t rec0, uint64_t *acc) {
     const uint64_t units = total / 32;
-    if (n <= 0 || units == 0) return hipSuccess;
-    hipLaunchKernelGGL(ppg_seq_query, dim3((unsigned)((units + 255) / 256)), dim3(256), 0, s, out, jobs, offs, oref, info,
-                       base, recs, cbase, seq_off, seq_len, units, *pat, m, hit_words, rec0, (unsigned long long *)acc, n);
+    if (v.n <= 0 || units == 0) return hipSuccess;
+    hipLaunchKernelGGL(ppg_seq_query, dim3((unsigned)((units + 255) / 256)), dim3(256), 0, s, v.out, v.jobs, v.offs, v.oref,
+                       v.info, v.base, v.recs, cbase, seq_off, seq_len, units, *pat, m, hit_words, rec0,
+                       (unsigned long long *)acc, v.n);
     return hipGetLastError();
 }
 
-hipError_t ppg_launch_seq_query_chunks(hipStream_t s, const PpgInflateResult *ires, const PpgParseInfo *info,
-                                       const uint64_t *base, int m, uint32_t *hit_words, uint64_t rec0, uint64_t *acc,
-                                       int64_t *host_chunk_hits, int n) {
-    if (n <= 0) return hipSuccess;
-    hipLaunchKernelGGL(ppg_seq_query_chunks, dim3(n), dim3(256), 0, s, ires, info, base, m, hit_words, rec0,
-                       (unsigned long long *)acc, host_chunk_hits, n);
+hipError_t ppg_launch_seq_query_chunks(hipStream_t s, const PpgBatchView &v, int m, uint32_t *hit_words, uint64_t rec0,
+                                       uint64_t *acc, int64_t *host_chunk_hits) {
+    if (v.n <= 0) return hipSuccess;
+    hipLaunchKernelGGL(ppg_seq_query_chunks, dim3(v.n), dim3(256), 0, s, v.res, v.info, v.base, m, hit_words, rec0,
+                       (unsigned long long *)acc, host_chunk_hits, v.n);
     return hipGetLastError();
 }
 

@@ -42,6 +42,7 @@
 #include <algorithm>
 #include "ppg_device.h"
 #include "ppg_launch.h"
+#include "ppg_seqload.h"
 
 namespace {
 
@@ -56,12 +57,6 @@ __device__ __forceinline__ void rec_text(const uint32_t *r, uint64_t q, uint32_t
     a = q ? r[4 * q - 1] + 1u : 0u;
     const uint32_t e = r[4 * q + 3] + 1u;
     len = e > a ? e - a : 0u;
-}
-
-__device__ __forceinline__ uint64_t wave_sum64(uint64_t v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_down((unsigned long long)v, o, 64);
-    return v;   // lane 0 holds the sum
 }
 
 __device__ __forceinline__ int32_t clamp_rel(int64_t v) {
@@ -388,13 +383,13 @@ extern "C" __global__ __launch_bounds__(256) void ppg_sel_copy(const int64_t *__
 }
 
 // ------------------------------------------------------------------------------------------
-// launchers (ppg_api.cpp, ppg_cursor.cpp); pointers at the batch's first chunk / record
+// launchers (ppg_stages.cpp); v: the batch (ppg_device.h)
 // ------------------------------------------------------------------------------------------
-hipError_t ppg_launch_sel_count(hipStream_t s, const PpgInflateResult *ires, const PpgParseInfo *info,
-                                const uint64_t *base, const uint32_t *recs, const uint32_t *mask, uint64_t bit0,
-                                uint64_t *crec, uint64_t *cbyte, int n) {
-    if (n <= 0) return hipSuccess;
-    hipLaunchKernelGGL(ppg_sel_count, dim3(n), dim3(256), 0, s, ires, info, base, recs, mask, bit0, crec, cbyte, n);
+hipError_t ppg_launch_sel_count(hipStream_t s, const PpgBatchView &v, const uint32_t *mask, uint64_t bit0, uint64_t *crec,
+                                uint64_t *cbyte) {
+    if (v.n <= 0) return hipSuccess;
+    hipLaunchKernelGGL(ppg_sel_count, dim3(v.n), dim3(256), 0, s, v.res, v.info, v.base, v.recs, mask, bit0, crec, cbyte,
+                       v.n);
     return hipGetLastError();
 }
 
@@ -404,15 +399,12 @@ hipError_t ppg_launch_sel_scan(hipStream_t s, const uint64_t *crec, const uint64
     return hipGetLastError();
 }
 
-hipError_t ppg_launch_sel_place(hipStream_t s, const PpgInflateResult *ires, const PpgParseInfo *info,
-                                const uint64_t *base, const uint32_t *recs, const uint32_t *mask, uint64_t bit0,
-                                const uint64_t *rbase, const uint64_t *bbase, const uint8_t *out, const PpgInflateJob *jobs,
-                                const uint8_t *offs, const PpgOffsetRef *oref, int64_t rec_lo, int64_t byte_lo,
-                                int64_t *recno, int64_t *sel_off, uint32_t *desc, PpgSelSrc *src, int64_t *span_first,
-                                int n) {
-    if (n <= 0) return hipSuccess;
-    hipLaunchKernelGGL(ppg_sel_place, dim3(n), dim3(256), 0, s, ires, info, base, recs, mask, bit0, rbase, bbase, out, jobs,
-                       offs, oref, rec_lo, byte_lo, recno, sel_off, (uint4 *)desc, src, span_first, n);
+hipError_t ppg_launch_sel_place(hipStream_t s, const PpgBatchView &v, const uint32_t *mask, uint64_t bit0,
+                                const uint64_t *rbase, const uint64_t *bbase, int64_t rec_lo, int64_t byte_lo,
+                                int64_t *recno, int64_t *sel_off, uint32_t *desc, PpgSelSrc *src, int64_t *span_first) {
+    if (v.n <= 0) return hipSuccess;
+    hipLaunchKernelGGL(ppg_sel_place, dim3(v.n), dim3(256), 0, s, v.res, v.info, v.base, v.recs, mask, bit0, rbase, bbase,
+                       v.out, v.jobs, v.offs, v.oref, rec_lo, byte_lo, recno, sel_off, (uint4 *)desc, src, span_first, v.n);
     return hipGetLastError();
 }
 

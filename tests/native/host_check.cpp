@@ -219,6 +219,47 @@ static void check_grouped_p2p() {
     }
 }
 
+// the host-only validators of the record stages (ppg_stages.cpp): one valid struct each, then invalid ones
+static void check_stage_validators() {
+    ppg_read_filter f = {};
+    f.criteria = 0xF;
+    f.min_len = 30;
+    f.max_len = 300;
+    f.qual_base = 33;
+    f.min_mean_milli = 20000;
+    f.low_q = 10;
+    f.max_low_milli = 500;
+    CHECK(ppg_read_filter_check(&f) == PPG_OK);
+    CHECK(ppg_read_filter_check(nullptr) == PPG_ARG_ERROR);
+    ppg_read_filter bad = f;
+    bad.criteria |= 0x20;   // an unknown bit
+    CHECK(ppg_read_filter_check(&bad) == PPG_ARG_ERROR);
+    bad = f;
+    bad.max_len = f.min_len - 1;
+    CHECK(ppg_read_filter_check(&bad) == PPG_ARG_ERROR);
+
+    ppg_read_trim t = {};
+    t.ops = 0xF;
+    t.qual_base = 33;
+    t.lead_q = t.trail_q = t.win_q = 20;
+    t.win_size = 4;
+    t.adapter_len = 12;
+    memcpy(t.adapter, "AGATCGGAAGAG", 12);
+    t.min_overlap = 3;
+    t.max_err_milli = 100;
+    CHECK(ppg_read_trim_check(&t) == PPG_OK);
+    CHECK(ppg_read_trim_check(nullptr) == PPG_ARG_ERROR);
+    ppg_read_trim tb = t;
+    tb.ops |= 0x20;   // an unknown bit
+    CHECK(ppg_read_trim_check(&tb) == PPG_ARG_ERROR);
+    tb = t;
+    tb.adapter[5] = '\n';
+    CHECK(ppg_read_trim_check(&tb) == PPG_ARG_ERROR);
+    tb = t;
+    tb.win_size = 33;
+    CHECK(ppg_read_trim_check(&tb) == PPG_ARG_ERROR);
+}
+
 int main(int argc, char **argv) {
     if (argc < 3) {
         fprintf(stderr, "usage: host_check <golden dir> <scratch dir>\n");
@@ -241,6 +282,7 @@ int main(int argc, char **argv) {
     for (int world : {2, 3, 5}) check_comm(g + "/l6_c200.gz", 200, world, 4);
     for (int world : {2, 3}) check_alltoallv(world);
     check_grouped_p2p();
+    check_stage_validators();
     printf("host_check: %s (%d failures)\n", failures ? "FAILED" : "ok", failures.load());
     return failures ? 1 : 0;
 }

@@ -306,6 +306,178 @@ def test_failed_run_leaves_hook_unready(device):
     assert sh.readtrim is None
 
 
+# ---- 3b. every stage beside the others: one layout per batch, no state left from one call to the next ----
+def assert_pack(pk, ref):
+    h = pk.to_host()
+    for key in ("seq_off", "seq_len", "bases", "mask", "qual"):
+        got = getattr(h, key)
+        assert got.dtype == ref[key].dtype and np.array_equal(got, ref[key]), key
+
+
+def assert_query(q, ref):
+    assert (q.records, q.hits, q.bases) == (ref["records"], ref["hits"], ref["bases"])
+    assert [q.counts[c] for c in pp.SeqQuery.CLASSES] == ref["counts"].tolist()
+    assert np.array_equal(q.chunk_hits, ref["chunk_hits"])
+
+
+def assert_filter(r, ref):
+    assert (r.records, r.passed) == (ref["records"], ref["passed"])
+    assert [r.failed[c] for c in pp.ReadFilterResult.CRITERIA] == ref["failed"].tolist()
+    assert (r.bases, r.other, r.qual_bytes) == (ref["bases"], ref["other"], ref["qual_bytes"])
+    assert np.array_equal(r.qual_count, ref["qual_count"]) and np.array_equal(r.chunk_passed, ref["chunk_passed"])
+
+
+def assert_selection(sel, ref):
+    h = sel.to_host()
+    assert (h.records, h.nbytes) == (ref["records"], ref["nbytes"])
+    for key in SEL_ARRAYS:
+        assert np.array_equal(getattr(h, key), ref[key]), key
+
+
+def test_all_hooks_at_once_then_pack_and_trim_alone(device):
+    """Keys, pack, query, filter (AND), trim (AND) and select attached together on several batches: every
+    stage gives its reference, over two runs.  Then the pack and the trim alone, the combination in which a
+    batch is laid out once from the run's carry (the pack's planes) and once from 0 (the trim's scratch)."""
+    import torch
+    from parallelparsing_amd import paired
+    from test_paired import _ref_keys
+    name, pattern, f, t = "memlevel1_c10", b"GATTAC", F.GOLDEN_FILTERS[2], T.ALL._replace(min_len=60)
+    ch = R.oracle_chunks(name)
+    kref = np.array([k for off, raw, desc in ch for k in _ref_keys(raw, desc, len(off))], np.int64)
+    pref, qref, fref, tref = R.reference(name), Q.reference(name, pattern), F.reference(name, f), T.reference(name, t)
+    three = qref["hit"] & fref["pass"] & tref["keep"]
+    assert 0 < three.sum() < qref["hits"]
+    sref = S.select_reference(ch, three)
+    nrec = tref["records"]
+    dev = torch.device("cuda", device.device)
+    sh = make_shard(name, device, out_capacity=8192)
+    assert sh.batches > 4
+    mask = torch.full((qref["mask"].size,), -1, dtype=torch.int32, device=dev)
+    rows = torch.full((nrec, 2), -1, dtype=torch.int32, device=dev)
+    pk = pp.PackedReads.empty(nrec, int(pref["seq_off"][-1]), True, device.device)
+    out = pp.SelectedRecords.empty(sref["records"], sref["nbytes"], device.device)
+    paired.attach_keys(sh, nrec)
+    sh.set_seqpack(pk).set_seqquery(pattern, mask).set_readfilter(_lib.PpgReadFilter(*f), mask, and_mask=True)
+    sh.set_readtrim(T.struct_of(t), mask, rows, and_mask=True).set_select(mask, out)
+    for _ in range(2):
+        sh.run()
+        assert np.array_equal(paired.shard_keys(sh).cpu().numpy(), kref)
+        assert sh.seqpack_ready
+        assert_pack(pk, pref)
+        assert_query(sh.seqquery, qref)
+        assert_filter(sh.readfilter, fref)
+        assert_totals(sh.readtrim, tref)
+        assert np.array_equal(sh.readtrim.chunk_kept, tref["chunk_kept"])
+        assert np.array_equal(sh.readtrim.windows_host(), tref["rows"])
+        assert np.array_equal(mask_words(mask), F.words_of(three))
+        assert_selection(sh.selected, sref)
+    # the pack and the trim alone, on the same shard
+    aref = T.reference(name, T.ALL)
+    sh.set_keys(None).set_seqquery(None).set_readfilter(None).set_select(None)
+    for plane in (pk.seq_off, pk.seq_len, pk.bases, pk.mask, pk.qual):
+        plane.fill_(0x5A)
+    mask.fill_(0x5A5A5A5A)
+    rows.fill_(0x5A5A5A5A)
+    sh.set_seqpack(pk).set_readtrim(T.struct_of(T.ALL), mask, rows).run()
+    assert sh.seqquery is None and sh.readfilter is None and sh.selected is None
+    assert sh.seqpack_ready
+    assert_pack(pk, pref)
+    assert_equals_reference(sh.readtrim, aref)
+    assert np.array_equal(mask_words(mask), aref["mask"])
+
+
+def test_one_shot_calls_in_any_order(device):
+    """On a one-batch shard after its run, every one-shot call between two trims: none depends on what the
+    one before it left in the shard's scratch."""
+    name, pattern, f = "memlevel1_c10", b"GATTAC", F.GOLDEN_FILTERS[4]
+    pref, qref, fref, tref = R.reference(name), Q.reference(name, pattern), F.reference(name, f), T.reference(name, T.ALL)
+    sh = make_shard(name, device).run()
+    assert sh.batches == 1
+    assert_equals_reference(sh.trim_reads(T.struct_of(T.ALL), mask=True, windows=True), tref)
+    assert_pack(sh.pack_sequences(), pref)
+    q = sh.query_sequences(pattern, mask=True)
+    assert_query(q, qref)
+    assert np.array_equal(mask_words(q.hit_mask)[:qref["mask"].size], qref["mask"])
+    assert sh.seq_bases() == (int(pref["seq_off"][-1]), pref["seq_len"].size)
+    r = sh.filter_reads(_lib.PpgReadFilter(*f), mask=True, metrics=True)
+    assert_filter(r, fref)
+    assert np.array_equal(mask_words(r.pass_mask)[:fref["mask"].size], fref["mask"])
+    got = r.metrics_host()
+    for field in F.METRICS_DTYPE.names:
+        assert np.array_equal(got[field], fref["metrics"][field]), field
+    assert_selection(sh.select_records(q), S.select_reference(R.oracle_chunks(name), qref["hit"]))
+    assert_equals_reference(sh.trim_reads(T.struct_of(T.ALL), mask=True, windows=True), tref)
+    assert sh.seqquery is None and sh.readfilter is None and sh.readtrim is None and sh.selected is None
+
+
+def _probe(name, *argtypes):
+    fn = getattr(_lib.lib, name)
+    fn.restype, fn.argtypes = C.c_int, [C.c_void_p] + list(argtypes)
+    return fn
+
+
+def test_probe_hooks(device):
+    """The measurement hooks of tools/*_probe.py, called the way the tools call them with one repetition:
+    they succeed, report times and the sizes the references give, leave no hook result behind, and the
+    one-shot calls after them are unharmed."""
+    chunks, f, t, pattern = T.forged_chunks(), F.FILTERS[5], T.ALL, b"CTC"
+    hit = Q.query_reference(chunks, pattern)["hit"]
+    sref = S.select_reference(chunks, hit)
+    assert 0 < sref["records"] < hit.size
+    sh = shard_of(T.forged_gz(), T.FORGED_CHUNK, device)
+    sh.set_seqquery(pattern).set_readfilter(_lib.PpgReadFilter(*f)).set_readtrim(T.struct_of(t)).run()
+    assert sh.batches == 1 and all(r is not None for r in (sh.seqquery, sh.readfilter, sh.readtrim))
+    words = dev_words(F.words_of(hit), device)
+    device.after_torch()
+    fp = C.POINTER(C.c_float)
+    select = _probe("ppgx_seqselect_times", C.c_void_p, C.c_int64, C.c_int, fp, C.POINTER(C.c_int64))
+    pack = _probe("ppgx_seqpack_times", C.c_int, C.c_int, fp, C.POINTER(C.c_int64))
+    query = _probe("ppgx_seqquery_times", C.c_char_p, C.c_int32, C.c_int, fp)
+    filt = _probe("ppgx_readfilter_times", C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, fp)
+    trim = _probe("ppgx_readtrim_times", C.c_void_p, C.c_int, C.c_int, fp)
+    fs, ts = _lib.PpgReadFilter(*f), T.struct_of(t)
+    mptr, mcap = C.c_void_p(words.data_ptr()), 32 * words.numel()
+
+    def times(n, call):
+        ms = (C.c_float * n)(*([-1.0] * n))
+        assert call(ms) == _lib.PPG_OK
+        assert all(np.isfinite(v) and v >= 0 for v in ms), list(ms)
+
+    for reps in (1, 0):
+        ok = reps > 0
+        sz, by = (C.c_int64 * 3)(), (C.c_int64 * 2)()
+        calls = ((5, lambda ms: select(sh.handle, mptr, mcap, reps, ms, sz)),
+                 (4, lambda ms: pack(sh.handle, 1, reps, ms, by)),
+                 (4, lambda ms: query(sh.handle, pattern, len(pattern), reps, ms)),
+                 (4, lambda ms: query(sh.handle, None, 0, reps, ms)),
+                 (3, lambda ms: filt(sh.handle, C.byref(fs), 1, 1, 0, reps, ms)),
+                 (3, lambda ms: filt(sh.handle, C.byref(fs), 0, 0, 1, reps, ms)),
+                 (4, lambda ms: trim(sh.handle, C.byref(ts), 1, reps, ms)))
+        for n, call in calls:
+            if ok:
+                times(n, call)
+            else:
+                assert call((C.c_float * n)()) == _lib.PPG_ARG_ERROR
+        if ok:
+            assert (sz[0], sz[1]) == (sref["records"], sref["nbytes"])
+            assert sz[2] == by[1] == sum(len(raw) for _, raw, _ in chunks)
+            assert sh.seqquery is None and sh.readfilter is None and sh.readtrim is None
+    ms = (C.c_float * 4)()
+    assert filt(sh.handle, C.byref(struct_and(fs)), 1, 0, 0, 1, ms) == _lib.PPG_ARG_ERROR
+    assert trim(sh.handle, C.byref(T.struct_of(t, and_mask=True)), 1, 1, ms) == _lib.PPG_ARG_ERROR
+    fref = F.filter_reference(chunks, f)
+    r = sh.filter_reads(fs, mask=True, metrics=True)
+    assert_filter(r, fref)
+    assert np.array_equal(mask_words(r.pass_mask)[:fref["mask"].size], fref["mask"])
+    assert_equals_reference(sh.trim_reads(ts, mask=True, windows=True), T.forged_reference(t))
+
+
+def struct_and(f):
+    s = _lib.PpgReadFilter.from_buffer_copy(f)
+    s.criteria |= F.AND_MASK
+    return s
+
+
 # ---- 4. the cursor and BatchedFASTQ ----
 def _fields(r):
     return (r.identifier, r.sequence, r.other, r.quality)
