@@ -428,10 +428,11 @@ int ppg_shard_select_ready(ppg_shard *sh, int64_t *records, int64_t *bytes);
  *  ppg_shard_set_readfilter    any number of batches: from the next run on every batch is measured
  *                              while its output is resident, record numbers and totals carried across
  *                              batches.  The filter is copied at the call; a NULL filter turns it off.
- *                              A batch's hooks run in the order keys, pack, query, filter, trim, select: a
- *                              filter with AND_MASK on the query hook's mask sees this batch's hit
- *                              bits, and the select hook sees the product.  A run with more records
- *                              than a cap fails with PPG_BUF_ERROR.
+ *                              A batch's hooks run in the order keys, pack, query, filter, trim, select (a
+ *                              profile hook, "read profile" below, between trim and select): a filter
+ *                              with AND_MASK on the query hook's mask sees this batch's hit bits, and
+ *                              the select hook sees the product.  A run with more records than a cap
+ *                              fails with PPG_BUF_ERROR.
  *  ppg_shard_readfilter_ready  as ppg_shard_seqquery_ready. */
 typedef struct {
     int64_t criteria;        /* PPG_FILTER_* bits */
@@ -509,8 +510,8 @@ int ppg_shard_readfilter_ready(ppg_shard *sh, int64_t *chunk_passed, void *resul
  *                            ppg_shard_filter_reads.
  *  ppg_shard_set_readtrim    the hook, as ppg_shard_set_readfilter: the struct is copied at the call, a
  *                            NULL trim turns it off.  A batch's hooks run in the order keys, pack, query,
- *                            filter, trim, select: a trim with AND_MASK on the query's mask gives the
- *                            selection "hit, passes, and still min_len long after trimming".
+ *                            filter, trim, profile, select: a trim with AND_MASK on the query's mask gives the
+ *                            profile and the selection "hit, passes, and still min_len long after trimming".
  *  ppg_shard_readtrim_ready  as ppg_shard_readfilter_ready. */
 typedef struct {
     int64_t ops;             /* PPG_TRIM_* bits */
@@ -542,6 +543,84 @@ int ppg_shard_trim_reads(ppg_shard *sh, const void *trim, uint32_t *dev_keep_mas
 int ppg_shard_set_readtrim(ppg_shard *sh, const void *trim, uint32_t *dev_keep_mask, int64_t rec_cap, void *dev_trim,
                            int64_t trim_cap);
 int ppg_shard_readtrim_ready(ppg_shard *sh, int64_t *chunk_kept, void *result);
+
+/* ---- read profile: bases and qualities per read position, lengths, GC and mean quality per read ----
+ * The report of a QC tool: what the data looks like, and what it looks like after a filter and a trim.
+ * It is made on the GPU while the text is resident; a table of max_pos rows and one fixed struct leave
+ * the device.  S_j, L_j, Q_j, Lq_j are those of "read filters" above.
+ * A profile is a ppg_read_profile: four int64_t, passed as const void *.  flags is a set of bits:
+ * PPG_PROFILE_USE_MASK 1, PPG_PROFILE_USE_WINDOWS 2.  P = max_pos is the number of positions profiled.
+ * The window (s_j, w_j) of record j: (0, L_j) without USE_WINDOWS; with it, from row j of dev_windows (a
+ * trim's row format: two uint32 (start, len)), clamped: s_j = min(start, L_j), w_j = min(len, L_j - s_j).
+ * No row makes a kernel read outside S_j.
+ * profiled_j = chunk k's status is 0 and, with USE_MASK, bit j of dev_mask (the hit-mask format) is set.
+ * The mask and the rows are only read.  A failed chunk contributes nothing; records the reference parses
+ * twice count twice, as in the filters.  In exact integer arithmetic, for a profiled record:
+ *   per position  p < min(w_j, P), i = s_j + p: the class of S_j[i] ('A' 'C' 'G' 'T' upper case, or other)
+ *                 is counted in base[p]; if i < Lq_j the Quality byte c = Q_j[i] is counted: qual_n[p] += 1,
+ *                 qual_sum[p] += c (the raw byte), qhist[p][b] += 1 with b = min(max(c - qual_base, 0), 63).
+ *                 Quality bytes at i >= L_j belong to no base and are counted nowhere.
+ *   per record    over the whole window, positions at and past P included: gc_j = its 'G' and 'C' bytes,
+ *                 qn_j = the i in the window with i < Lq_j, qsum_j = the sum of those Quality bytes.
+ * `table` (optional): host memory, table_cap rows of 72 int64_t (ppg_read_profile_row); the first P are
+ * written.  len_here of row p counts the profiled records with w_j == p (row 0: the empty ones).
+ * `result` (optional) points at a ppg_read_profile_result: records counts the records of decoded chunks;
+ * longer the profiled records with w_j >= P, which no len_here counts; bases the sum of w_j,
+ * bases_profiled of min(w_j, P), qual_bytes of qn_j; no_quality the profiled records with w_j > 0 and
+ * qn_j == 0; gc_hist[100 * gc_j / w_j] counts the records with w_j > 0; meanq_hist counts those with
+ * qn_j > 0 in bin 0 if qsum_j <= qual_base * qn_j, else min(63, (qsum_j - qual_base * qn_j) / qn_j).
+ * chunk_profiled (optional): host int64[n], the profiled records per chunk.  Every output is a function
+ * of the text, the struct, the mask and the rows alone.
+ * ppg_read_profile_check is host only: PPG_ARG_ERROR for a NULL profile, unknown flag bits, qual_base
+ * outside [0, 255], max_pos outside [1, PPG_PROFILE_MAX_POS], a reserved field that is not 0; PPG_OK
+ * otherwise.  Every entry point below applies it.  PPG_ARG_ERROR as well for a flag without its buffer, a
+ * buffer without its flag, a mask that is not 4-byte aligned, a mask_cap that is not a multiple of 32, rows
+ * that are not 8-byte aligned.  records > mask_cap (with a mask) or > windows_cap (with rows), or a table
+ * with table_cap < max_pos: PPG_BUF_ERROR, nothing written.
+ *  ppg_shard_profile_reads      a one-batch shard after its run, blocking; PPG_ARG_ERROR as for
+ *                               ppg_shard_trim_reads.
+ *  ppg_shard_set_readprofile    the hook, as ppg_shard_set_readtrim: the struct is copied at the call, a
+ *                               NULL profile turns it off; the accumulators are carried across a run's
+ *                               batches and restart with its first.  A batch's hooks run in the order
+ *                               keys, pack, query, filter, trim, profile, select: the profile reads the
+ *                               mask as the trim left it, so on the tensors that query, filter and trim
+ *                               write with AND_MASK it describes exactly the reads the selection hands over.
+ *  ppg_shard_readprofile_ready  as ppg_shard_readtrim_ready; the table of the hook's max_pos rows
+ *                               (table_cap too small: PPG_BUF_ERROR, nothing written). */
+enum { PPG_PROFILE_USE_MASK = 1, PPG_PROFILE_USE_WINDOWS = 2, PPG_PROFILE_MAX_POS = 1024 };
+typedef struct {
+    int64_t flags;           /* PPG_PROFILE_* bits */
+    int64_t qual_base;       /* the Quality byte of quality 0 (33 for Sanger / Illumina 1.8+) */
+    int64_t max_pos;         /* P: positions profiled, 1 .. PPG_PROFILE_MAX_POS */
+    int64_t reserved;        /* 0 */
+} ppg_read_profile;
+typedef struct {
+    int64_t base[5];         /* A, C, G, T, other */
+    int64_t qual_n;
+    int64_t qual_sum;
+    int64_t len_here;        /* profiled records whose window is this long */
+    int64_t qhist[64];
+} ppg_read_profile_row;
+typedef struct {
+    int64_t records;         /* records of decoded chunks */
+    int64_t profiled;
+    int64_t longer;          /* w_j >= max_pos */
+    int64_t bases;           /* sum of w_j */
+    int64_t bases_profiled;  /* sum of min(w_j, max_pos) */
+    int64_t qual_bytes;      /* sum of qn_j */
+    int64_t no_quality;      /* w_j > 0 and qn_j == 0 */
+    int64_t reserved;
+    int64_t gc_hist[101];
+    int64_t meanq_hist[64];
+} ppg_read_profile_result;
+int ppg_read_profile_check(const void *profile);
+int ppg_shard_profile_reads(ppg_shard *sh, const void *profile, const uint32_t *dev_mask, int64_t mask_cap,
+                            const void *dev_windows, int64_t windows_cap, int64_t *chunk_profiled, void *result,
+                            int64_t *table, int64_t table_cap);
+int ppg_shard_set_readprofile(ppg_shard *sh, const void *profile, const uint32_t *dev_mask, int64_t mask_cap,
+                              const void *dev_windows, int64_t windows_cap);
+int ppg_shard_readprofile_ready(ppg_shard *sh, int64_t *chunk_profiled, void *result, int64_t *table,
+                                int64_t table_cap);
 
 /* Device-resident per-chunk record counts (int64[n]) copied to caller device memory on this
  * GPU (the input of the cross-GPU all-gather). */

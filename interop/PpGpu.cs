@@ -121,6 +121,31 @@ public unsafe struct PpgReadTrimResult  // ppg_read_trim_result
     public long BasesKept;
 }
 
+[StructLayout(LayoutKind.Sequential)]
+public struct PpgReadProfile            // ppg_read_profile
+{
+    public const long UseMask = 1, UseWindows = 2, MaxPositions = 1024;
+    public long Flags;                  // the bits above
+    public long QualBase;               // the Quality byte of quality 0 (33)
+    public long MaxPos;                 // positions profiled, 1 .. MaxPositions
+    public long Reserved;               // 0
+}
+
+[StructLayout(LayoutKind.Sequential)]
+public unsafe struct PpgReadProfileResult  // ppg_read_profile_result
+{
+    public long Records;
+    public long Profiled;
+    public long Longer;                 // window >= MaxPos
+    public long Bases;
+    public long BasesProfiled;
+    public long QualBytes;
+    public long NoQuality;
+    public long Reserved;
+    public fixed long GcHist[101];
+    public fixed long MeanqHist[64];
+}
+
 internal static unsafe class PpGpu
 {
     const string Lib = "ppgpu";   // libppgpu.so from parallelparsing_amd/
@@ -222,6 +247,16 @@ internal static unsafe class PpGpu
     [DllImport(Lib)] public static extern int ppg_shard_set_readtrim(nint shard, void* trim, uint* devKeepMask,
         long recCap, void* devTrim, long trimCap);
     [DllImport(Lib)] public static extern int ppg_shard_readtrim_ready(nint shard, long* chunkKept, void* result);
+    // read profile: bases and qualities per read position, lengths, GC and mean quality per read (profile: a
+    // PpgReadProfile*, result: a PpgReadProfileResult*, table: host rows of 72 longs; mask and rows are device
+    // pointers and only read)
+    [DllImport(Lib)] public static extern int ppg_read_profile_check(void* profile);
+    [DllImport(Lib)] public static extern int ppg_shard_profile_reads(nint shard, void* profile, uint* devMask,
+        long maskCap, void* devWindows, long windowsCap, long* chunkProfiled, void* result, long* table, long tableCap);
+    [DllImport(Lib)] public static extern int ppg_shard_set_readprofile(nint shard, void* profile, uint* devMask,
+        long maskCap, void* devWindows, long windowsCap);
+    [DllImport(Lib)] public static extern int ppg_shard_readprofile_ready(nint shard, long* chunkProfiled, void* result,
+        long* table, long tableCap);
     // record selection: the records a mask selects, compacted on the GPU (device pointers; a null mask
     // with maskCap 0 selects every record)
     [DllImport(Lib)] public static extern int ppg_shard_select_size(nint shard, uint* devMask, long maskCap,

@@ -818,6 +818,81 @@ class ReadTrimResult:
                 f"bases={self.bases}, bases_window={self.bases_window}, bases_kept={self.bases_kept})")
 
 
+class ReadProfile:
+    """A read profile (include/ppgpu.h "read profile"): bases and qualities of the first max_positions read
+    positions (1 .. 1024), read lengths, GC content and mean quality per read.  quality_base is the Quality
+    byte of quality 0; the quality histograms have 64 bins above it."""
+
+    def __init__(self, max_positions=256, qual_base=33):
+        self.max_positions, self.qual_base = max_positions, qual_base
+
+    def struct(self, use_mask=False, use_windows=False):
+        """The ppg_read_profile of this profile (with the USE_MASK / USE_WINDOWS bits); ValueError when
+        ppg_read_profile_check refuses it."""
+        flags = (_lib.PPG_PROFILE_USE_MASK if use_mask else 0) | (_lib.PPG_PROFILE_USE_WINDOWS if use_windows else 0)
+        p = _lib.PpgReadProfile(flags, int(self.qual_base), int(self.max_positions), 0)
+        if lib.ppg_read_profile_check(C.byref(p)) != 0:
+            raise ValueError(f"ReadProfile: not a valid profile: {self!r}")
+        return p
+
+    def __repr__(self):
+        return f"ReadProfile(max_positions={self.max_positions}, qual_base={self.qual_base})"
+
+
+def _profile_struct(profile, use_mask=False, use_windows=False):
+    """The ppg_read_profile of a ReadProfile, or of a _lib.PpgReadProfile with its flags set for the buffers."""
+    if isinstance(profile, ReadProfile):
+        return profile.struct(use_mask, use_windows)
+    if not isinstance(profile, _lib.PpgReadProfile):
+        raise ValueError("expected a ReadProfile")
+    return ReadProfile(profile.max_pos, profile.qual_base).struct(use_mask, use_windows)
+
+
+class ReadProfileResult:
+    """The result of a read profile (include/ppgpu.h "read profile"): the totals `records`, `profiled`,
+    `longer` (windows of at least max_positions bases, which length_hist does not count), `bases`,
+    `bases_profiled`, `qual_bytes`, `no_quality`; `gc_hist` (numpy int64[101]: reads by GC percent),
+    `meanq_hist` (int64[64]: reads by mean quality), `chunk_profiled` (int64, profiled records per chunk)
+    and `table`, a numpy structured array of one row per position (base[5], qual_n, qual_sum, len_here,
+    qhist[64]).  base_counts, mean_quality and length_hist are views / derivations of the table."""
+
+    CLASSES = ("A", "C", "G", "T", "other")
+    ROW_DTYPE = np.dtype([("base", "<i8", (5,)), ("qual_n", "<i8"), ("qual_sum", "<i8"), ("len_here", "<i8"),
+                          ("qhist", "<i8", (64,))])
+
+    def __init__(self, result, table, chunk_profiled=None, qual_base=33):
+        for name in ("records", "profiled", "longer", "bases", "bases_profiled", "qual_bytes", "no_quality"):
+            setattr(self, name, int(getattr(result, name)))
+        self.gc_hist = np.array(result.gc_hist, np.int64)
+        self.meanq_hist = np.array(result.meanq_hist, np.int64)
+        self.table = np.ascontiguousarray(table, np.int64).reshape(-1, 72).view(self.ROW_DTYPE).reshape(-1)
+        self.chunk_profiled = chunk_profiled
+        self.qual_base = qual_base
+
+    @property
+    def base_counts(self):
+        """int64[positions, 5]: the bases A, C, G, T and other at every position."""
+        return self.table["base"]
+
+    @property
+    def length_hist(self):
+        """int64[positions]: the profiled reads by the length of their window (`longer` holds the rest)."""
+        return self.table["len_here"]
+
+    @property
+    def mean_quality(self):
+        """float64[positions]: the mean quality above qual_base at every position, nan where no Quality
+        byte was counted.  Derived on the host from qual_sum and qual_n."""
+        n = self.table["qual_n"].astype(np.float64)
+        with np.errstate(divide="ignore", invalid="ignore"):
+            return np.where(n > 0, self.table["qual_sum"] / n - self.qual_base, np.nan)
+
+    def __repr__(self):
+        return (f"ReadProfileResult(records={self.records}, profiled={self.profiled}, longer={self.longer}, "
+                f"bases={self.bases}, bases_profiled={self.bases_profiled}, qual_bytes={self.qual_bytes}, "
+                f"no_quality={self.no_quality}, positions={self.table.shape[0]})")
+
+
 class SelectedRecords:
     """The records a mask selects (include/ppgpu.h "record selection"): `bytes` (uint8, the selected
     records' text back to back), `sel_off` (int64, records + 1 offsets into it), `desc` (records x 4:
@@ -1255,6 +1330,62 @@ class Shard:
             return None
         rt = getattr(self, "_rt", None) or (None, None)
         return ReadTrimResult(res, ch, rt[0], rt[1])
+
+    def _profile_args(self, profile, mask, windows, what):
+        """(struct, mask pointer, mask_cap, rows pointer, rows cap, tensors to keep alive) of a profile call"""
+        ptr, cap, mask = _mask_arg(mask, what)
+        wptr, wcap = None, 0
+        if windows is not None:
+            import torch
+            if not (hasattr(windows, "data_ptr") and windows.is_cuda and windows.dtype in (torch.int32, torch.uint32)
+                    and windows.is_contiguous()):
+                raise ValueError(f"{what}: windows must be a contiguous int32 / uint32 CUDA tensor")
+            wcap = windows.numel() // 2
+            wptr = C.c_void_p(windows.data_ptr()) if wcap else None
+        p = _profile_struct(profile, ptr is not None, wptr is not None)
+        return p, ptr, cap, wptr, wcap if wptr is not None else 0, (mask, windows)
+
+    def profile_reads(self, profile, mask=None, windows=None):
+        """The read profile `profile` (a ReadProfile) over the records of a one-batch shard after its run
+        (ppg_shard_profile_reads), as a ReadProfileResult.  mask: hit-mask words (a SeqQuery with a mask
+        or an int32 / uint32 CUDA tensor): only the records whose bit is set are profiled; windows: an
+        int32 / uint32 CUDA tensor of (start, len) rows (a trim's): each record is profiled inside its
+        window.  Both are only read.  Ordered after torch's stream, complete on return."""
+        p, ptr, cap, wptr, wcap, _ = self._profile_args(profile, mask, windows, "profile_reads")
+        self._torch_order()
+        res, ch = _lib.PpgReadProfileResult(), np.zeros(self.n, np.int64)
+        table = np.zeros((int(p.max_pos), 72), np.int64)
+        check(lib.ppg_shard_profile_reads(self._h, C.byref(p), ptr, cap, wptr, wcap, _ptr(ch), C.byref(res),
+                                          _ptr(table), table.shape[0]), "profile_reads")
+        return ReadProfileResult(res, table, ch, int(p.qual_base))
+
+    def set_readprofile(self, profile, mask=None, windows=None):
+        """From the next run on, every output batch is profiled by `profile` while its output is resident
+        (ppg_shard_set_readprofile): works for shards of any number of batches, and runs after the
+        set_seqquery, set_readfilter and set_readtrim hooks and before a set_select hook, so it reads the
+        mask and the windows those have written; the result is `readprofile` after the run.  mask and
+        windows as in profile_reads, sized for the whole shard.  profile=None turns it off."""
+        if profile is None:
+            check(lib.ppg_shard_set_readprofile(self._h, None, None, 0, None, 0), "set_readprofile")
+            self._rp = None
+            return self
+        p, ptr, cap, wptr, wcap, keep = self._profile_args(profile, mask, windows, "set_readprofile")
+        self._rp = (keep, int(p.max_pos), int(p.qual_base))   # kept alive while the library may read them
+        self._torch_order()
+        check(lib.ppg_shard_set_readprofile(self._h, C.byref(p), ptr, cap, wptr, wcap), "set_readprofile")
+        return self
+
+    @property
+    def readprofile(self):
+        """The ReadProfileResult of the last run's set_readprofile hook, or None when that run did not complete one."""
+        rp = getattr(self, "_rp", None)
+        if rp is None:
+            return None
+        res, ch = _lib.PpgReadProfileResult(), np.zeros(self.n, np.int64)
+        table = np.zeros((rp[1], 72), np.int64)
+        if lib.ppg_shard_readprofile_ready(self._h, _ptr(ch), C.byref(res), _ptr(table), table.shape[0]) != 1:
+            return None
+        return ReadProfileResult(res, table, ch, rp[2])
 
     def select_size(self, mask=None):
         """(records, bytes) a selection by `mask` holds, after a run of any number of batches
@@ -1788,20 +1919,53 @@ class BatchedFASTQ:
             self._qshard = (cap, sh)
         return sh
 
+    def _stage_shard(self):
+        """The query shard with every record-stage hook off: each Count* / Profile attaches its own."""
+        return self._query_shard().set_seqquery(None).set_readfilter(None).set_readtrim(None).set_readprofile(None)
+
     def _query(self, pattern):
-        return self._query_shard().set_readfilter(None).set_readtrim(None).set_seqquery(pattern).run().seqquery
+        return self._stage_shard().set_seqquery(pattern).run().seqquery
 
     def CountPassing(self, filter):   # noqa: A002
         """The ReadFilterResult of `filter` (a ReadFilter) over the file: how many records pass, how many
         fail each criterion, and the totals, measured on the GPU batch by batch (Shard.set_readfilter):
         no record text reaches the host."""
-        return self._query_shard().set_seqquery(None).set_readtrim(None).set_readfilter(filter).run().readfilter
+        return self._stage_shard().set_readfilter(filter).run().readfilter
 
     def CountTrimmed(self, trim):
         """The ReadTrimResult of `trim` (a ReadTrim) over the file: how many records each cut moves, how
         many are kept and the bases left, measured on the GPU batch by batch (Shard.set_readtrim): totals
         alone, no record text and no window reaches the host."""
-        return self._query_shard().set_seqquery(None).set_readfilter(None).set_readtrim(trim).run().readtrim
+        return self._stage_shard().set_readtrim(trim).run().readtrim
+
+    def Profile(self, profile=None, pattern=None, filter=None, trim=None):   # noqa: A002
+        """The ReadProfileResult of the file: bases and qualities per read position, read lengths, GC
+        content and mean quality per read (profile: a ReadProfile, None for the default), made on the GPU
+        batch by batch (Shard.set_readprofile).  With pattern / filter / trim it is the profile of the
+        reads that contain the pattern, pass the filter and are kept by the trim, inside the trim's
+        windows: one mask tensor and one rows tensor are chained through the hooks on the device, and
+        nothing but the result leaves it."""
+        sh = self._stage_shard()
+        profile = ReadProfile() if profile is None else profile
+        if pattern is None and filter is None and trim is None:
+            return sh.set_readprofile(profile).run().readprofile
+        import torch
+        dev = torch.device("cuda", sh.dev.device)
+        nrec = getattr(sh, "_profile_records", None)
+        if nrec is None:   # the tensors' sizes: one run without hooks counts the records
+            nrec = sh._profile_records = max(sh.run().total_records, 0)
+        mask = torch.full(((nrec + 31) // 32 + 1,), -1, dtype=torch.int32, device=dev)
+        rows = torch.zeros((nrec + 1, 2), dtype=torch.int32, device=dev) if trim is not None else None
+        if pattern is not None:
+            sh.set_seqquery(pattern, mask=mask)   # writes the words; the later stages AND into them
+        if filter is not None:
+            sh.set_readfilter(filter, mask=mask, and_mask=True)
+        if trim is not None:
+            sh.set_readtrim(trim, mask=mask, windows=rows, and_mask=True)
+        try:
+            return sh.set_readprofile(profile, mask=mask, windows=rows).run().readprofile
+        finally:
+            sh.set_seqquery(None).set_readfilter(None).set_readtrim(None).set_readprofile(None)
 
     def QualityCounts(self):
         """numpy int64[256]: the bytes of every Quality line by value, counted on the GPU batch by batch."""

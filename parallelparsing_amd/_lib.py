@@ -137,6 +137,10 @@ _SIGS = {
     "ppg_cursor_open_trim": (C.c_int, [vp, vp, C.c_char_p, i32, i32, i64, C.c_int, vp, i32, vp, vp, P(vp)]),
     "ppg_cursor_selected_trim": (C.c_int, [vp, P(vp)]),
     "ppg_cursor_trim_result": (C.c_int, [vp, vp]),
+    "ppg_read_profile_check": (C.c_int, [vp]),
+    "ppg_shard_profile_reads": (C.c_int, [vp, vp, vp, i64, vp, i64, vp, vp, vp, i64]),
+    "ppg_shard_set_readprofile": (C.c_int, [vp, vp, vp, i64, vp, i64]),
+    "ppg_shard_readprofile_ready": (C.c_int, [vp, vp, vp, vp, i64]),
     "ppg_shard_select_size": (C.c_int, [vp, vp, i64, P(i64), P(i64)]),
     "ppg_shard_select_records": (C.c_int, [vp, vp, i64, vp, vp, vp, i64, vp, i64, P(i64), P(i64)]),
     "ppg_shard_set_select": (C.c_int, [vp, vp, i64, vp, vp, vp, i64, vp, i64]),
@@ -221,6 +225,21 @@ class PpgReadTrimResult(C.Structure):
 
 
 PPG_TRIM_LEADING, PPG_TRIM_TRAILING, PPG_TRIM_WINDOW, PPG_TRIM_ADAPTER, PPG_TRIM_AND_MASK = 1, 2, 4, 8, 0x100
+
+
+class PpgReadProfile(C.Structure):
+    """ppg_read_profile (include/ppgpu.h)."""
+    _fields_ = [("flags", C.c_int64), ("qual_base", C.c_int64), ("max_pos", C.c_int64), ("reserved", C.c_int64)]
+
+
+class PpgReadProfileResult(C.Structure):
+    """ppg_read_profile_result (include/ppgpu.h)."""
+    _fields_ = [("records", C.c_int64), ("profiled", C.c_int64), ("longer", C.c_int64), ("bases", C.c_int64),
+                ("bases_profiled", C.c_int64), ("qual_bytes", C.c_int64), ("no_quality", C.c_int64),
+                ("reserved", C.c_int64), ("gc_hist", C.c_int64 * 101), ("meanq_hist", C.c_int64 * 64)]
+
+
+PPG_PROFILE_USE_MASK, PPG_PROFILE_USE_WINDOWS, PPG_PROFILE_MAX_POS = 1, 2, 1024
 
 
 for _name, (_res, _args) in _SIGS.items():

@@ -121,6 +121,26 @@ struct PpgReadTrim {
 // cut[5], bases, bases_window, bases_kept)
 constexpr int kRtAcc = 11;
 
+// a ppg_read_profile (include/ppgpu.h "read profile") as the profile kernels' argument
+struct PpgReadProfile {
+    int64_t flags, qual_base, max_pos, reserved;
+};
+// the read profile's accumulators: the int64 fields of a ppg_read_profile_result in order (records, profiled,
+// longer, bases, bases_profiled, qual_bytes, no_quality, reserved, gc_hist[101], meanq_hist[64]), then the
+// table: max_pos rows of kRpRow values (base[5], qual_n, qual_sum, len_here, qhist[64])
+constexpr int kRpFixed = 173, kRpRow = 72, kRpMaxPos = 1024;
+// ppg_rp_measure's LDS, in 32-bit counters: 7 planes (base[5], qual_n, qual_sum) of kRpStride(max_pos)
+// positions and the quality rows of the first kRpTile(max_pos), both multiples of 32.  80 KiB at most: two
+// blocks stay resident per CU (160 KiB).  All of 256 positions fit (72 KiB); of 1,024, 192 quality rows.
+constexpr int kRpLdsWords = 20480;
+constexpr int kRpStride(int max_pos) { return (max_pos + 31) & ~31; }
+constexpr int kRpTile(int max_pos) {
+    return ((kRpLdsWords - 7 * kRpStride(max_pos)) / 64 & ~31) < kRpStride(max_pos)
+               ? ((kRpLdsWords - 7 * kRpStride(max_pos)) / 64 & ~31)
+               : kRpStride(max_pos);
+}
+static_assert(kRpTile(256) == 256 && kRpTile(kRpMaxPos) == 192 && kRpTile(1) == 32, "ppg_rp_measure's quality rows");
+
 // ppg_sel_copy: the destination bytes one workgroup writes (256 threads x 4 words of 16 B); ppg_sel_place
 // records, per multiple of it inside a batch's destination range, the selected record that holds that byte
 constexpr uint32_t kSelSpan = 16384;

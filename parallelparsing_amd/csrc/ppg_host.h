@@ -163,8 +163,9 @@ struct StageLayout {
     int64_t total = 0;              // padded bases of the batch laid out last
 };
 
-// What query, filter and trim each carry: the run's accumulators on the device, and what the kernels store
-// to pinned memory, the result struct followed by one count per chunk of the shard.
+// What query, filter, trim and profile each carry: the run's accumulators on the device, and what the kernels
+// store to pinned memory, the result struct (the profile's table after it) followed by one count per chunk of
+// the shard.
 struct StageOut {
     int on = 0;        // attached: every batch of a run goes through the stage
     int written = 0;   // the last successful run completed it (stages_run_end)
@@ -224,6 +225,22 @@ struct TrimStage : StageOut {
     uint32_t *rows = nullptr;
     int64_t rows_cap = 0;
     DevBuf<uint32_t> rsc;   // scratch: four planes (lead, win, adapt, trail) of one batch's records
+};
+
+// ppg_shard_set_readprofile: every batch's records are also profiled (ppg_readprofile.hip); the mask and the
+// (start, len) rows are read at the shard record number.  acc and host: kRpFixed + kRpRow * max_pos values,
+// the fixed result and then the table; host has the chunk counts after them.
+struct ProfileStage : StageOut {
+    PpgReadProfile prf = {};
+    const uint32_t *mask = nullptr;
+    int64_t mask_cap = 0;
+    const uint32_t *rows = nullptr;
+    int64_t rows_cap = 0;
+    int grid = 0;             // ppg_rp_measure's blocks (ppgx_readprofile_grid); 0: the launcher's default
+    int cus = 0;              // the device's CUs, asked for once
+    int64_t out_pos = 0;      // max_pos of what host holds
+    DevBuf<uint64_t> rsc;     // scratch: gc | qn << 32 and qsum of one batch's records
+    int64_t values() const { return kRpFixed + (int64_t)kRpRow * out_pos; }
 };
 
 // ppg_shard_set_select: every batch's selected records are also appended to these buffers
@@ -290,6 +307,7 @@ struct ppg_shard {
     QueryStage query;
     FilterStage filter;
     TrimStage trim;
+    ProfileStage profile;
     SelectStage select;
     // split chunks (ppg_shard_set_split): the inflate launch runs sub-jobs, ppg_split_merge folds
     // them back into per-chunk results and census regions
@@ -338,7 +356,7 @@ bool pread_parallel(int fd, uint8_t *dst, int64_t off, int64_t len, int threads)
 // descriptor; rec0: its first record's shard record number; tot: its records.  Everything is queued on the
 // shard's stream; the calls said to block synchronise it. ----
 PpgBatchView batch_view(const ppg_shard *sh, int32_t b0, int32_t b1, const uint32_t *recs);
-// batch_collect's one call: the batch's hooks in the order keys, pack, query, filter, trim, select
+// batch_collect's one call: the batch's hooks in the order keys, pack, query, filter, trim, profile, select
 int shard_batch_hooks(ppg_shard *sh, int32_t b0, int32_t b1, int64_t tot);
 // ppg_shard_run's two: no hook's output counts as written during a run; a run that succeeded wrote them all
 void stages_run_begin(ppg_shard *sh);
@@ -369,6 +387,11 @@ int shard_read_filter(ppg_shard *sh, int32_t b0, int32_t b1, const uint32_t *rec
 int shard_read_trim(ppg_shard *sh, int32_t b0, int32_t b1, const uint32_t *recs, int64_t rec0, int64_t tot,
                     const PpgReadTrim &trm, uint32_t *mask, uint32_t *rows, bool first);
 bool readtrim_ok(const void *trim, PpgReadTrim *out);
+// read profile, after shard_layout of the same chunks; mask and rows (both at the shard's record 0) may be
+// null.  The totals so far, the table and the chunks' profiled records are in profile.host once the stream
+// has drained.
+int shard_read_profile(ppg_shard *sh, int32_t b0, int32_t b1, const uint32_t *recs, int64_t rec0, int64_t tot,
+                       const PpgReadProfile &prf, const uint32_t *mask, const uint32_t *rows, bool first);
 // record selection (record j of the batch has bit bit0 + j of mask, a null mask selects all).  sizes: the
 // selected records and their bytes (blocks).  move: after sizes of the same chunks, queues the selection into
 // the buffers from output record rec_lo and byte byte_lo on; recno counts from bit0.

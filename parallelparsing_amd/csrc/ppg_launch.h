@@ -107,6 +107,17 @@ PPG_WEAK hipError_t ppg_launch_rt_totals(hipStream_t s, const uint64_t *acc, int
 PPG_WEAK hipError_t ppg_launch_rt_gather(hipStream_t s, const uint32_t *trim, const int64_t *recno, int64_t rec0,
                                          uint64_t n, uint32_t *dst);
 
+// ---- ppg_readprofile.hip ----
+// Weak for the same reason (readprofile_linked, ppg_stages.cpp).
+PPG_WEAK hipError_t ppg_launch_rp_measure(hipStream_t s, const PpgBatchView &v, const uint64_t *cbase,
+                                          const int64_t *seq_off, const uint32_t *seq_len, uint64_t total,
+                                          const PpgReadProfile *prf, const uint32_t *words, const uint32_t *rows,
+                                          uint64_t rec0, uint64_t *rsc, uint64_t *acc, int blocks, int cus);
+PPG_WEAK hipError_t ppg_launch_rp_finish(hipStream_t s, const PpgBatchView &v, const uint64_t *rsc,
+                                         const PpgReadProfile *prf, const uint32_t *words, const uint32_t *rows,
+                                         uint64_t rec0, uint64_t *acc, int64_t *host_chunk_profiled);
+PPG_WEAK hipError_t ppg_launch_rp_totals(hipStream_t s, const uint64_t *acc, int64_t *host_result, uint32_t n);
+
 // ---- ppg_seqselect.hip ----
 // Weak for the same reason (select_linked, ppg_stages.cpp).
 PPG_WEAK hipError_t ppg_launch_sel_count(hipStream_t s, const PpgBatchView &v, const uint32_t *mask, uint64_t bit0,

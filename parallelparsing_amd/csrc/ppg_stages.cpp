@@ -1,11 +1,12 @@
 // ppg_stages.cpp — the record stages of libppgpu.so: work on a batch of a shard while its output is resident
 // on the GPU.  Packed reads (ppg_seqpack.hip), sequence query (ppg_seqquery.hip), read filter
-// (ppg_readfilter.hip), read trim (ppg_readtrim.hip) and record selection (ppg_seqselect.hip): for each its
+// (ppg_readfilter.hip), read trim (ppg_readtrim.hip), read profile (ppg_readprofile.hip) and record selection
+// (ppg_seqselect.hip): for each its
 // pieces on one batch, its C entry points (one-shot on a one-batch shard, the hook of every batch of a
 // run, and what the last run left) and the measurement hook of its tools/*_probe.py.
 //
 // A batch's hooks run from one place, shard_batch_hooks, called once by batch_collect (ppg_api.cpp).  The
-// unit kernels of query, filter and trim read one layout of the batch (StageLayout, ppg_host.h), which
+// unit kernels of query, filter, trim and profile read one layout of the batch (StageLayout, ppg_host.h), which
 // their caller makes with shard_layout once per batch before the first of them.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -20,7 +21,8 @@
 
 // the result structs are the kernels' accumulators in order; the chunk counts follow them in pinned memory
 static_assert(sizeof(ppg_seq_query_result) == 8 * 8 && sizeof(ppg_read_filter_result) == 8 * kRfAcc &&
-                  sizeof(ppg_read_trim_result) == 8 * kRtAcc,
+                  sizeof(ppg_read_trim_result) == 8 * kRtAcc && sizeof(ppg_read_profile_result) == 8 * kRpFixed &&
+                  sizeof(ppg_read_profile) == sizeof(PpgReadProfile) && PPG_PROFILE_MAX_POS == kRpMaxPos,
               "a stage's result struct is its accumulators");
 
 static bool seq_linked() {   // (weak references, ppg_launch.h: absent from the host-only sanitizer build)
@@ -37,6 +39,10 @@ static bool readfilter_linked() {
 
 static bool readtrim_linked() {
     return seq_linked() && ppg_launch_rt_measure && ppg_launch_rt_decide && ppg_launch_rt_totals && ppg_launch_rt_gather;
+}
+
+static bool readprofile_linked() {
+    return seq_linked() && ppg_launch_rp_measure && ppg_launch_rp_finish && ppg_launch_rp_totals;
 }
 
 static bool select_linked() {
@@ -260,6 +266,60 @@ int shard_read_trim(ppg_shard *sh, int32_t b0, int32_t b1, const uint32_t *recs,
     return PPG_OK;
 }
 
+// ---- read profile (ppg_readprofile.hip) ----
+// the rules of include/ppgpu.h "read profile"; host only
+static bool readprofile_ok(const void *profile, PpgReadProfile *out) {
+    if (!profile) return false;
+    PpgReadProfile p;
+    memcpy(&p, profile, sizeof p);
+    if (p.flags & ~(int64_t)(PPG_PROFILE_USE_MASK | PPG_PROFILE_USE_WINDOWS)) return false;
+    if (p.qual_base < 0 || p.qual_base > 255) return false;
+    if (p.max_pos < 1 || p.max_pos > kRpMaxPos || p.reserved != 0) return false;
+    if (out) *out = p;
+    return true;
+}
+
+// each flag with its buffer and each buffer with its flag
+static bool readprofile_bufs_ok(const PpgReadProfile &p, const uint32_t *mask, int64_t mask_cap, const void *rows,
+                                int64_t rows_cap) {
+    if (!seqquery_mask_ok(mask, mask_cap) || ((p.flags & PPG_PROFILE_USE_MASK) != 0) != (mask != nullptr)) return false;
+    if (((p.flags & PPG_PROFILE_USE_WINDOWS) != 0) != (rows != nullptr)) return false;
+    return rows_cap >= 0 && ((uintptr_t)rows & 7) == 0 && (rows != nullptr || rows_cap == 0);
+}
+
+int shard_read_profile(ppg_shard *sh, int32_t b0, int32_t b1, const uint32_t *recs, int64_t rec0, int64_t tot,
+                       const PpgReadProfile &prf, const uint32_t *mask, const uint32_t *rows, bool first) {
+    hipStream_t s = shard_stream(sh);
+    const PpgBatchView v = batch_view(sh, b0, b1, recs);
+    ProfileStage &p = sh->profile;
+    if (!readprofile_linked()) return PPG_UNSUPPORTED;
+    if (!p.cus) HIPCHK(hipDeviceGetAttribute(&p.cus, hipDeviceAttributeMultiprocessorCount, sh->ctx->device));
+    HIPCHK(grow_buf(p.rsc, 2 * ((size_t)tot + 1)));
+    p.out_pos = prf.max_pos;
+    if (int rc = stage_out_begin(sh, p, (int)p.values(), first)) return rc;
+    if (tot) HIPCHK(hipMemsetAsync(p.rsc.p, 0, 16 * (size_t)tot, s));
+    HIPCHK(ppg_launch_rp_measure(s, v, sh->lay.cbase.p, sh->lay.off.p, sh->lay.len.p, (uint64_t)sh->lay.total, &prf, mask,
+                                 rows, (uint64_t)rec0, p.rsc.p, p.acc.p, p.grid, p.cus));
+    HIPCHK(ppg_launch_rp_finish(s, v, p.rsc.p, &prf, mask, rows, (uint64_t)rec0, p.acc.p, p.result() + p.values() + b0));
+    HIPCHK(ppg_launch_rp_totals(s, p.acc.p, p.result(), (uint32_t)p.values()));
+    return PPG_OK;
+}
+
+// what the last completed profile left in pinned memory (n: the shard's chunks; P: its max_pos); the caller
+// has checked the table's cap
+static void readprofile_outputs(const ProfileStage &p, int32_t n, int64_t P, int64_t *chunk_profiled, void *result,
+                                int64_t *table) {
+    const size_t fixed = 8 * (size_t)kRpFixed, rows = 8 * (size_t)kRpRow * (size_t)P;
+    if (!p.host.p) {   // a shard without chunks: no batch ran
+        if (result) memset(result, 0, fixed);
+        if (table) memset(table, 0, rows);
+        return;
+    }
+    if (result) memcpy(result, p.host.p, fixed);
+    if (table) memcpy(table, p.host.p + fixed, rows);
+    if (chunk_profiled && n) memcpy(chunk_profiled, p.host.p + fixed + rows, 8 * (size_t)n);
+}
+
 // ---- record selection (ppg_seqselect.hip) ----
 int shard_select_reserve(ppg_shard *sh, int64_t nchunks) {
     HIPCHK(sh->select.ccnt.alloc(2 * ((size_t)nchunks + 1)));
@@ -321,11 +381,11 @@ static int select_hook(ppg_shard *sh, int32_t b0, int32_t b1, const uint32_t *re
 
 // ---- a batch's hooks ----
 // Everything attached to the shard, on the batch [b0, b1) of tot records that batch_collect has just waited
-// for, in the order keys, pack, query, filter, trim, select.  The batch's output is resident: the next
-// batch's inflate follows on the same stream, so it is read before it is overwritten.  A filter with
-// AND_MASK on the query's mask sees this batch's hit bits, a trim what both have left of them, and the
-// selection, last, the product.  A cap that the batch would exceed fails with PPG_BUF_ERROR before the
-// stage writes anything.
+// for, in the order keys, pack, query, filter, trim, profile, select.  The batch's output is resident: the
+// next batch's inflate follows on the same stream, so it is read before it is overwritten.  A filter with
+// AND_MASK on the query's mask sees this batch's hit bits, a trim what both have left of them, the profile
+// reads the mask and the rows as the trim left them, and the selection, last, hands over the product.  A cap
+// that the batch would exceed fails with PPG_BUF_ERROR before the stage writes anything.
 int shard_batch_hooks(ppg_shard *sh, int32_t b0, int32_t b1, int64_t tot) {
     const int64_t rec0 = sh->total_records, after = rec0 + tot;
     const uint32_t *recs = sh->recs.p + 4 * (uint64_t)rec0;
@@ -345,10 +405,12 @@ int shard_batch_hooks(ppg_shard *sh, int32_t b0, int32_t b1, int64_t tot) {
     const QueryStage &q = sh->query;
     const FilterStage &f = sh->filter;
     const TrimStage &t = sh->trim;
-    if (q.on || f.on || t.on) {   // the unit kernels' layout, once for the three
+    const ProfileStage &p = sh->profile;
+    if (q.on || f.on || t.on || p.on) {   // the unit kernels' layout, once for the four
         if (q.on && q.mask && after > q.rec_cap) return PPG_BUF_ERROR;
         if (f.on && ((f.mask && after > f.rec_cap) || (f.metrics && after > f.metrics_cap))) return PPG_BUF_ERROR;
         if (t.on && ((t.mask && after > t.rec_cap) || (t.rows && after > t.rows_cap))) return PPG_BUF_ERROR;
+        if (p.on && ((p.mask && after > p.mask_cap) || (p.rows && after > p.rows_cap))) return PPG_BUF_ERROR;
         if (int rc = shard_layout(sh, b0, b1, recs, tot)) return rc;
     }
     if (q.on)
@@ -357,13 +419,16 @@ int shard_batch_hooks(ppg_shard *sh, int32_t b0, int32_t b1, int64_t tot) {
         if (int rc = shard_read_filter(sh, b0, b1, recs, rec0, tot, f.flt, f.mask, f.metrics, first)) return rc;
     if (t.on)
         if (int rc = shard_read_trim(sh, b0, b1, recs, rec0, tot, t.trm, t.mask, t.rows, first)) return rc;
+    if (p.on)
+        if (int rc = shard_read_profile(sh, b0, b1, recs, rec0, tot, p.prf, p.mask, p.rows, first)) return rc;
     if (sh->select.on)
         if (int rc = select_hook(sh, b0, b1, recs, tot)) return rc;
     return PPG_OK;
 }
 
 void stages_run_begin(ppg_shard *sh) {
-    sh->keys_written = sh->pack.written = sh->query.written = sh->filter.written = sh->trim.written = sh->select.written = 0;
+    sh->keys_written = sh->pack.written = sh->query.written = sh->filter.written = sh->trim.written = sh->profile.written = 0;
+    sh->select.written = 0;
 }
 
 void stages_run_end(ppg_shard *sh, bool ok) {
@@ -372,6 +437,7 @@ void stages_run_end(ppg_shard *sh, bool ok) {
     sh->query.written = ok && sh->query.on;
     sh->filter.written = ok && sh->filter.on;
     sh->trim.written = ok && sh->trim.on;
+    sh->profile.written = ok && sh->profile.on;
     sh->select.written = ok && sh->select.on;
 }
 
@@ -632,6 +698,57 @@ int ppg_shard_readtrim_ready(ppg_shard *sh, int64_t *chunk_kept, void *result) {
     if (!sh) return PPG_ARG_ERROR;
     if (!sh->trim.written) return 0;
     sh->trim.outputs(sh->n, chunk_kept, result, sizeof(ppg_read_trim_result));
+    return 1;
+}
+
+// ---- read profile: the read trimming entry points' counterparts ----
+int ppg_read_profile_check(const void *profile) { return readprofile_ok(profile, nullptr) ? PPG_OK : PPG_ARG_ERROR; }
+
+int ppg_shard_profile_reads(ppg_shard *sh, const void *profile, const uint32_t *dev_mask, int64_t mask_cap,
+                            const void *dev_windows, int64_t windows_cap, int64_t *chunk_profiled, void *result,
+                            int64_t *table, int64_t table_cap) {
+    PpgReadProfile prf;
+    if (!sh || !sh->ran || sh->batches.size() != 1 || !readprofile_ok(profile, &prf) ||
+        !readprofile_bufs_ok(prf, dev_mask, mask_cap, dev_windows, windows_cap))
+        return PPG_ARG_ERROR;
+    if (!readprofile_linked()) return PPG_UNSUPPORTED;
+    if ((dev_mask && sh->total_records > mask_cap) || (dev_windows && sh->total_records > windows_cap) ||
+        (table && table_cap < prf.max_pos))
+        return PPG_BUF_ERROR;
+    HIPCHK(hipSetDevice(sh->ctx->device));
+    sh->profile.written = 0;   // the pinned outputs are rewritten: an earlier run's hook result is gone
+    if (int rc = shard_layout(sh, 0, sh->n, sh->recs.p, sh->total_records)) return rc;
+    if (int rc = shard_read_profile(sh, 0, sh->n, sh->recs.p, 0, sh->total_records, prf, dev_mask,
+                                    (const uint32_t *)dev_windows, true))
+        return rc;
+    HIPCHK(hipStreamSynchronize(shard_stream(sh)));
+    readprofile_outputs(sh->profile, sh->n, prf.max_pos, chunk_profiled, result, table);
+    return PPG_OK;
+}
+
+int ppg_shard_set_readprofile(ppg_shard *sh, const void *profile, const uint32_t *dev_mask, int64_t mask_cap,
+                              const void *dev_windows, int64_t windows_cap) {
+    if (!sh) return PPG_ARG_ERROR;
+    PpgReadProfile prf = {};
+    if (profile && (!readprofile_ok(profile, &prf) || !readprofile_bufs_ok(prf, dev_mask, mask_cap, dev_windows, windows_cap)))
+        return PPG_ARG_ERROR;
+    ProfileStage &p = sh->profile;
+    p.on = profile ? 1 : 0;
+    p.prf = prf;
+    p.mask = profile ? dev_mask : nullptr;
+    p.mask_cap = profile ? mask_cap : 0;
+    p.rows = profile ? (const uint32_t *)dev_windows : nullptr;
+    p.rows_cap = profile ? windows_cap : 0;
+    p.written = 0;   // completed by the next run, not by an earlier one
+    return PPG_OK;
+}
+
+int ppg_shard_readprofile_ready(ppg_shard *sh, int64_t *chunk_profiled, void *result, int64_t *table, int64_t table_cap) {
+    if (!sh) return PPG_ARG_ERROR;
+    const ProfileStage &p = sh->profile;
+    if (!p.written) return 0;
+    if (table && table_cap < p.prf.max_pos) return PPG_BUF_ERROR;
+    readprofile_outputs(p, sh->n, p.prf.max_pos, chunk_profiled, result, table);
     return 1;
 }
 
@@ -925,6 +1042,52 @@ int ppgx_readtrim_times(ppg_shard *sh, const void *trim, int with_mask, int reps
                 return e != hipSuccess ? e : ppg_launch_rt_totals(s, t.acc.p, t.result());
         }
     });
+}
+
+// tools/readprofile_probe.py.  ms[0..2]: the layout, the measure kernel with the zeroing of its scratch, and
+// the finish kernel + the totals' store; mask / windows as ppg_shard_profile_reads takes them.
+int ppgx_readprofile_times(ppg_shard *sh, const void *profile, const uint32_t *dev_mask, int64_t mask_cap,
+                           const void *dev_windows, int64_t windows_cap, int reps, float *ms) {
+    PpgReadProfile prf;
+    if (!sh || !sh->ran || sh->batches.size() != 1 || !ms || reps < 1 || !readprofile_ok(profile, &prf) ||
+        !readprofile_bufs_ok(prf, dev_mask, mask_cap, dev_windows, windows_cap) ||
+        (dev_mask && sh->total_records > mask_cap) || (dev_windows && sh->total_records > windows_cap))
+        return PPG_ARG_ERROR;
+    HIPCHK(hipSetDevice(sh->ctx->device));
+    hipStream_t s = shard_stream(sh);
+    const int64_t tot = sh->total_records;
+    const uint32_t *rows = (const uint32_t *)dev_windows;
+    ProfileStage &p = sh->profile;
+    p.written = 0;
+    if (int rc = shard_layout(sh, 0, sh->n, sh->recs.p, tot)) return rc;
+    if (int rc = shard_read_profile(sh, 0, sh->n, sh->recs.p, 0, tot, prf, dev_mask, rows, true)) return rc;
+    HIPCHK(hipStreamSynchronize(s));
+    const StageLayout &lay = sh->lay;
+    const PpgBatchView v = whole_view(sh);
+    return time_steps(s, 3, reps, ms, [&](int step) {
+        hipError_t e = hipSuccess;
+        switch (step) {
+            case 0:
+                e = launch_totals_scan(sh, s);
+                return e != hipSuccess ? e : launch_offsets(sh, s, lay.off.p, lay.len.p);
+            case 1:
+                if (tot) e = hipMemsetAsync(p.rsc.p, 0, 16 * (size_t)tot, s);
+                if (e != hipSuccess) return e;
+                return ppg_launch_rp_measure(s, v, lay.cbase.p, lay.off.p, lay.len.p, (uint64_t)lay.total, &prf, dev_mask, rows,
+                                             0, p.rsc.p, p.acc.p, p.grid, p.cus);
+            default:
+                e = ppg_launch_rp_finish(s, v, p.rsc.p, &prf, dev_mask, rows, 0, p.acc.p, p.result() + p.values());
+                return e != hipSuccess ? e : ppg_launch_rp_totals(s, p.acc.p, p.result(), (uint32_t)p.values());
+        }
+    });
+}
+
+// ppg_rp_measure's grid on this shard from now on (0: the default, the blocks resident on the device).  The tests force the
+// blocks' tile loop and uneven shares at small sizes with it.
+int ppgx_readprofile_grid(ppg_shard *sh, int blocks) {
+    if (!sh || blocks < 0) return PPG_ARG_ERROR;
+    sh->profile.grid = blocks;
+    return PPG_OK;
 }
 
 }  // extern "C"

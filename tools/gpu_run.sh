@@ -32,6 +32,8 @@
 #   readtrim[:args]             tools/readtrim_probe.py: read trim kernels against ppg_rf_measure and ppg_seq_query,
 #                               CountTrimmed and Where(trim) against Where(filter) and the text cursor
 #                               -> profiles/readtrim_probe.json + readtrim_probe.log
+#   readprofile[:args]          tools/readprofile_probe.py: read profile kernels against ppg_rf_measure and ppg_seq_query,
+#                               Profile() against CountPassing -> profiles/readprofile_probe.json + readprofile_probe.log
 set -o pipefail
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT" || exit 1
 tag=$1; shift
@@ -132,6 +134,11 @@ run_step() {
       > $O/readtrim_probe.out 2> $O/readtrim_probe.log || { tail -5 $O/readtrim_probe.log; return 1; }
     cp profiles/readtrim_probe.json $O/
     python3 -c "import json,sys; d=json.load(open(sys.argv[1])); print(json.dumps(d['kernels'])[:2500]); print(d['file']); print({k: (round(v['records_per_s']/1e6,1), v['bytes_to_host']) for k, v in d['from_file'].items()})" $O/readtrim_probe.json ;;
+  readprofile)
+    timeout -k 10 500 python3 -u tools/readprofile_probe.py $xa \
+      > $O/readprofile_probe.out 2> $O/readprofile_probe.log || { tail -5 $O/readprofile_probe.log; return 1; }
+    cp profiles/readprofile_probe.json $O/
+    python3 -c "import json,sys; d=json.load(open(sys.argv[1])); print(json.dumps(d['kernels'])[:2500]); print(d['file']); print({k: (round(v['records_per_s']/1e6,1), v['bytes_to_host']) for k, v in d['from_file'].items()})" $O/readprofile_probe.json ;;
   *)
     echo "gpu_run.sh: unknown step $step" >&2; return 2 ;;
   esac
