@@ -429,7 +429,8 @@ int ppg_shard_select_ready(ppg_shard *sh, int64_t *records, int64_t *bytes);
  *                              while its output is resident, record numbers and totals carried across
  *                              batches.  The filter is copied at the call; a NULL filter turns it off.
  *                              A batch's hooks run in the order keys, pack, query, filter, trim, select (a
- *                              profile hook, "read profile" below, between trim and select): a filter
+ *                              dedup hook, "read dedup" below, and a profile hook, "read profile" below,
+ *                              in that order between trim and select): a filter
  *                              with AND_MASK on the query hook's mask sees this batch's hit bits, and
  *                              the select hook sees the product.  A run with more records than a cap
  *                              fails with PPG_BUF_ERROR.
@@ -510,8 +511,9 @@ int ppg_shard_readfilter_ready(ppg_shard *sh, int64_t *chunk_passed, void *resul
  *                            ppg_shard_filter_reads.
  *  ppg_shard_set_readtrim    the hook, as ppg_shard_set_readfilter: the struct is copied at the call, a
  *                            NULL trim turns it off.  A batch's hooks run in the order keys, pack, query,
- *                            filter, trim, profile, select: a trim with AND_MASK on the query's mask gives the
- *                            profile and the selection "hit, passes, and still min_len long after trimming".
+ *                            filter, trim, dedup, profile, select: a trim with AND_MASK on the query's mask
+ *                            gives the dedup, the profile and the selection "hit, passes, and still min_len
+ *                            long after trimming".
  *  ppg_shard_readtrim_ready  as ppg_shard_readfilter_ready. */
 typedef struct {
     int64_t ops;             /* PPG_TRIM_* bits */
@@ -582,9 +584,10 @@ int ppg_shard_readtrim_ready(ppg_shard *sh, int64_t *chunk_kept, void *result);
  *  ppg_shard_set_readprofile    the hook, as ppg_shard_set_readtrim: the struct is copied at the call, a
  *                               NULL profile turns it off; the accumulators are carried across a run's
  *                               batches and restart with its first.  A batch's hooks run in the order
- *                               keys, pack, query, filter, trim, profile, select: the profile reads the
- *                               mask as the trim left it, so on the tensors that query, filter and trim
- *                               write with AND_MASK it describes exactly the reads the selection hands over.
+ *                               keys, pack, query, filter, trim, profile, select (a dedup hook, "read
+ *                               dedup" below, between trim and profile): the profile reads the mask as
+ *                               those left it, so on the tensors that query, filter, trim and dedup write
+ *                               with AND_MASK it describes exactly the reads the selection hands over.
  *  ppg_shard_readprofile_ready  as ppg_shard_readtrim_ready; the table of the hook's max_pos rows
  *                               (table_cap too small: PPG_BUF_ERROR, nothing written). */
 enum { PPG_PROFILE_USE_MASK = 1, PPG_PROFILE_USE_WINDOWS = 2, PPG_PROFILE_MAX_POS = 1024 };
@@ -621,6 +624,101 @@ int ppg_shard_set_readprofile(ppg_shard *sh, const void *profile, const uint32_t
                               const void *dev_windows, int64_t windows_cap);
 int ppg_shard_readprofile_ready(ppg_shard *sh, int64_t *chunk_profiled, void *result, int64_t *table,
                                 int64_t table_cap);
+
+/* ---- read dedup: first occurrences by a 64-bit fingerprint, and the duplication levels ----
+ * fastp's --dedup and FastQC's "Sequence Duplication Levels": the one step of a QC pipeline that needs
+ * memory across reads.  Here that memory is a hash table in caller device memory that persists across the
+ * batches of a run, so "has not been seen before" is one more bit in the mask that query, filter and trim
+ * AND into, and the duplication report is one struct.  S_j, L_j, record numbering, failed chunks and
+ * twice-parsed records (they count twice, so the second is a duplicate of the first) are as in
+ * "read filters" above.
+ * A dedup is a ppg_read_dedup: four int64_t, passed as const void *.  flags is a set of bits:
+ * PPG_DEDUP_USE_WINDOWS 2, PPG_DEDUP_AND_MASK 0x100.
+ * Key bytes D_j.  The window (s_j, w_j) of record j is the profile's: (0, L_j) without USE_WINDOWS; with it,
+ * from row j of dev_windows (a trim's row format: two uint32 (start, len)), clamped: s_j = min(start, L_j),
+ * w_j = min(len, L_j - s_j).  D_j = S_j[s_j, s_j + Ld_j) with Ld_j = w_j when max_bases == 0 and
+ * min(w_j, max_bases) otherwise (max_bases = 50 is FastQC's rule).  No row makes a kernel read outside S_j;
+ * the rows are only read.
+ * Participation.  part_j = chunk k's status is 0 and, with AND_MASK, bit j of the mask is set.
+ * Fingerprint.  64 bits, in exact unsigned arithmetic mod 2^64:
+ *   unit i of D_j  the bytes D_j[32 i, 32 i + 32), zero-padded to 32, as four little-endian uint64 w_0 .. w_3;
+ *   mix(x)         x ^= x >> 32; x *= 0xD6E8FEB86659FD93; x ^= x >> 32; x *= 0xD6E8FEB86659FD93; x ^= x >> 32;
+ *   h_i            a = mix(0x9E3779B97F4A7C15 * (i + 1)), then a = mix(a ^ w_t) for t = 0, 1, 2, 3; h_i = a;
+ *   G_j            the sum of h_i over i < ceil(Ld_j / 32) (0 when Ld_j = 0);
+ *   F_j            mix(G_j ^ mix(Ld_j + 0x632BE59BD9B4E019)); an F_j of 0 becomes 1.
+ * Two participating records are duplicates of each other if and only if their F is equal.  This is a
+ * fingerprint dedup, like fastp's, not a byte compare: records with equal key bytes always have equal F, and
+ * records with different key bytes have equal F with the probability of a 64-bit collision.  For N
+ * participating records the chance of at least one false merge is about N^2 / 2^65: about 2e-7 at 2.88 M
+ * records, about 4e-3 at 4e8.
+ * The table.  dev_table is caller device memory, 8-byte aligned: `slots` rows of three uint64 {key, first,
+ * count}; slots is a power of two, at least 64.  An empty row has key 0, first all ones, count 0.  The home
+ * slot of F is (F * 0x9E3779B97F4A7C15) >> (64 - log2 slots), with linear probing and wrap.  After a run, for
+ * every distinct F among the participants exactly one row has key = F, first = the lowest shard record number
+ * with that F and count = the number of participants with it; every other row is empty.  Which row holds a
+ * key is unspecified; the set of rows is a function of the text, the struct, the mask and the windows alone.
+ * The run's first batch makes the whole table empty, and so does the one-shot call.
+ * Capacity.  A batch that would bring 2 x (the records of the run so far, this batch included) above slots
+ * fails with PPG_BUF_ERROR before the stage writes anything: the load never exceeds 1/2 and every probe ends
+ * at an empty row.
+ * Per-record outputs, final when the batch's hooks return (earlier batches hold the lower record numbers):
+ * unique_j = part_j and first(F_j) == j.  dev_unique_mask: the hit-mask format, 4-byte aligned, mask_cap a
+ * multiple of 32; optional without AND_MASK, and then written like a query's mask (every word below
+ * ceil(records / 32) whole, pad bits 0, nothing at or past mask_cap / 32); with AND_MASK it is required, bit
+ * j becomes old & unique_j and no other bit changes.  dev_first (optional): 8-byte aligned, first_cap rows of
+ * one int64: the record number of the first occurrence of F_j (j itself when unique), -1 for a record that
+ * does not participate.  chunk_unique (optional): host int64[n], the unique records per chunk.
+ * `result` (optional) points at a ppg_read_dedup_result: records counts the records of decoded chunks; bases
+ * the sum of Ld_j over the participants, bases_unique over the unique ones.  The levels are FastQC's bins of a
+ * row's count: 1, 2, ..., 9, 10-49, 50-99, 100-499, 500-999, 1000-4999, 5000-9999, >= 10000.
+ * level_distinct[b] counts the rows in bin b, level_reads[b] sums their counts: the sum of level_distinct is
+ * unique, the sum of level_reads is participating.  max_count and max_first are the count and first of the
+ * row with the greatest count, ties going to the lowest first; 0 and -1 for an empty table.  overflow counts
+ * the inserts that found no row within slots probes: 0 under the capacity rule; it exists so that a broken
+ * probe ends and shows.  The counters are carried across a run's batches; the levels and the greatest row are
+ * made once, after the run's last batch.
+ * ppg_read_dedup_check is host only: PPG_ARG_ERROR for a NULL dedup, unknown flag bits, max_bases < 0, a
+ * reserved field that is not 0; PPG_OK otherwise.  Every entry point below applies it.  PPG_ARG_ERROR as well
+ * for AND_MASK without a mask, USE_WINDOWS without windows, windows without USE_WINDOWS, a misaligned buffer,
+ * a mask_cap that is not a multiple of 32, a cap without its buffer, slots that is not a power of two or is
+ * below 64, a NULL table.  records > mask_cap (with a mask), > windows_cap (with windows), > first_cap (with
+ * dev_first) or > slots / 2: PPG_BUF_ERROR, nothing written.
+ *  ppg_shard_dedup_reads      a one-batch shard after its run, blocking; PPG_ARG_ERROR as for
+ *                             ppg_shard_trim_reads.
+ *  ppg_shard_set_readdedup    the hook, as ppg_shard_set_readtrim: the struct is copied at the call, a NULL
+ *                             dedup turns it off; the table and the counters are carried across a run's
+ *                             batches and restart with its first.  A batch's hooks run in the order keys,
+ *                             pack, query, filter, trim, dedup, profile, select: the dedup sees what query,
+ *                             filter and trim left of the mask, and the trim's windows; the profile and the
+ *                             selection see only first occurrences.
+ *  ppg_shard_readdedup_ready  as ppg_shard_readtrim_ready.
+ * A rank of a multi-GPU job deduplicates its own share alone: its table sees no other rank's records. */
+enum { PPG_DEDUP_USE_WINDOWS = 2, PPG_DEDUP_AND_MASK = 0x100 };
+typedef struct {
+    int64_t flags;           /* PPG_DEDUP_* bits */
+    int64_t max_bases;       /* 0: the whole window; else the key is its first max_bases bases */
+    int64_t reserved[2];     /* 0 */
+} ppg_read_dedup;
+typedef struct {
+    int64_t records;         /* records of decoded chunks */
+    int64_t participating;
+    int64_t unique;          /* first occurrences: the rows of the table */
+    int64_t bases;           /* sum of Ld_j over the participants */
+    int64_t bases_unique;    /* ... over the unique records */
+    int64_t overflow;        /* inserts that found no row: 0 */
+    int64_t max_count;       /* the greatest count of a row */
+    int64_t max_first;       /* ... and that row's first (ties: the lowest); -1 for an empty table */
+    int64_t level_distinct[16];
+    int64_t level_reads[16];
+} ppg_read_dedup_result;
+int ppg_read_dedup_check(const void *dedup);
+int ppg_shard_dedup_reads(ppg_shard *sh, const void *dedup, uint32_t *dev_unique_mask, int64_t mask_cap,
+                          const void *dev_windows, int64_t windows_cap, int64_t *dev_first, int64_t first_cap,
+                          void *dev_table, int64_t slots, int64_t *chunk_unique, void *result);
+int ppg_shard_set_readdedup(ppg_shard *sh, const void *dedup, uint32_t *dev_unique_mask, int64_t mask_cap,
+                            const void *dev_windows, int64_t windows_cap, int64_t *dev_first, int64_t first_cap,
+                            void *dev_table, int64_t slots);
+int ppg_shard_readdedup_ready(ppg_shard *sh, int64_t *chunk_unique, void *result);
 
 /* Device-resident per-chunk record counts (int64[n]) copied to caller device memory on this
  * GPU (the input of the cross-GPU all-gather). */

@@ -146,6 +146,30 @@ public unsafe struct PpgReadProfileResult  // ppg_read_profile_result
     public fixed long MeanqHist[64];
 }
 
+[StructLayout(LayoutKind.Sequential)]
+public unsafe struct PpgReadDedup       // ppg_read_dedup
+{
+    public const long UseWindows = 2, AndMask = 0x100;
+    public long Flags;                  // the bits above
+    public long MaxBases;               // 0: the whole window; 50: FastQC's rule
+    public fixed long Reserved[2];      // 0
+}
+
+[StructLayout(LayoutKind.Sequential)]
+public unsafe struct PpgReadDedupResult  // ppg_read_dedup_result
+{
+    public long Records;
+    public long Participating;
+    public long Unique;
+    public long Bases;
+    public long BasesUnique;
+    public long Overflow;               // 0
+    public long MaxCount;
+    public long MaxFirst;               // -1: an empty table
+    public fixed long LevelDistinct[16];  // rows with a count of 1 .. 9, 10-49, 50-99, 100-499, 500-999, 1000-4999, 5000-9999, >= 10000
+    public fixed long LevelReads[16];
+}
+
 internal static unsafe class PpGpu
 {
     const string Lib = "ppgpu";   // libppgpu.so from parallelparsing_amd/
@@ -257,6 +281,15 @@ internal static unsafe class PpGpu
         long maskCap, void* devWindows, long windowsCap);
     [DllImport(Lib)] public static extern int ppg_shard_readprofile_ready(nint shard, long* chunkProfiled, void* result,
         long* table, long tableCap);
+    // read dedup: first occurrences by a 64-bit fingerprint and the duplication levels (dedup: a PpgReadDedup*,
+    // result: a PpgReadDedupResult*; mask, rows, first and the table of slots x 3 ulongs are device pointers)
+    [DllImport(Lib)] public static extern int ppg_read_dedup_check(void* dedup);
+    [DllImport(Lib)] public static extern int ppg_shard_dedup_reads(nint shard, void* dedup, uint* devUniqueMask,
+        long maskCap, void* devWindows, long windowsCap, long* devFirst, long firstCap, void* devTable, long slots,
+        long* chunkUnique, void* result);
+    [DllImport(Lib)] public static extern int ppg_shard_set_readdedup(nint shard, void* dedup, uint* devUniqueMask,
+        long maskCap, void* devWindows, long windowsCap, long* devFirst, long firstCap, void* devTable, long slots);
+    [DllImport(Lib)] public static extern int ppg_shard_readdedup_ready(nint shard, long* chunkUnique, void* result);
     // record selection: the records a mask selects, compacted on the GPU (device pointers; a null mask
     // with maskCap 0 selects every record)
     [DllImport(Lib)] public static extern int ppg_shard_select_size(nint shard, uint* devMask, long maskCap,

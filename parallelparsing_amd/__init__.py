@@ -893,6 +893,87 @@ class ReadProfileResult:
                 f"no_quality={self.no_quality}, positions={self.table.shape[0]})")
 
 
+class ReadDedup:
+    """A read dedup (include/ppgpu.h "read dedup"): reads are duplicates of each other when the 64-bit
+    fingerprints of their key bytes are equal.  The key is the read, or its trim window, cut to its first
+    max_bases bases (0: all of it; 50 is FastQC's rule)."""
+
+    def __init__(self, max_bases=0):
+        self.max_bases = max_bases
+
+    def struct(self, and_mask=False, use_windows=False):
+        """The ppg_read_dedup of this dedup (with the AND_MASK / USE_WINDOWS bits); ValueError when
+        ppg_read_dedup_check refuses it."""
+        flags = (_lib.PPG_DEDUP_AND_MASK if and_mask else 0) | (_lib.PPG_DEDUP_USE_WINDOWS if use_windows else 0)
+        d = _lib.PpgReadDedup(flags, int(self.max_bases), (C.c_int64 * 2)(0, 0))
+        if lib.ppg_read_dedup_check(C.byref(d)) != 0:
+            raise ValueError(f"ReadDedup: not a valid dedup: {self!r}")
+        return d
+
+    @staticmethod
+    def min_slots(records):
+        """The smallest legal table for a run of `records` records: a power of two, at least 64 and 2 x records."""
+        return max(64, 1 << max(2 * int(records) - 1, 0).bit_length())
+
+    def __repr__(self):
+        return f"ReadDedup(max_bases={self.max_bases})"
+
+
+def _dedup_struct(dedup, and_mask=False, use_windows=False):
+    """The ppg_read_dedup of a ReadDedup, or of a _lib.PpgReadDedup with its flags set for the buffers."""
+    if isinstance(dedup, ReadDedup):
+        return dedup.struct(and_mask, use_windows)
+    if not isinstance(dedup, _lib.PpgReadDedup):
+        raise ValueError("expected a ReadDedup")
+    return ReadDedup(dedup.max_bases).struct(and_mask, use_windows)
+
+
+class ReadDedupResult:
+    """The result of a read dedup (include/ppgpu.h "read dedup"): the totals `records`, `participating`,
+    `unique`, `bases`, `bases_unique`, `overflow`, `max_count`, `max_first`; `level_distinct` and `level_reads`
+    (numpy int64[16]: the table's rows and their reads by FastQC's duplication level, LEVELS names the bins);
+    `chunk_unique` (int64, unique records per chunk); `duplication_rate` = 1 - unique / participating; and the
+    device tensors of the call: `unique_mask` (uint32 hit-mask words), `first` (int64 per record: the first
+    occurrence's record number, -1 when the record does not participate) and `table` (int64 [slots, 3]: key,
+    first, count; an empty row is 0, -1, 0), each None when not asked for."""
+
+    TOTALS = ("records", "participating", "unique", "bases", "bases_unique", "overflow", "max_count", "max_first")
+    LEVELS = ("1", "2", "3", "4", "5", "6", "7", "8", "9", ">10", ">50", ">100", ">500", ">1k", ">5k", ">10k")
+
+    def __init__(self, result, chunk_unique=None, unique_mask=None, first=None, table=None):
+        for name in self.TOTALS:
+            setattr(self, name, int(getattr(result, name)))
+        self.level_distinct = np.array(result.level_distinct, np.int64)
+        self.level_reads = np.array(result.level_reads, np.int64)
+        self.chunk_unique = chunk_unique
+        self.unique_mask, self.first, self.table = unique_mask, first, table
+
+    @property
+    def duplication_rate(self):
+        return 1.0 - self.unique / self.participating if self.participating else 0.0
+
+    def top(self, k):
+        """[(count, first)] of the k rows with the greatest counts (fewer when the table holds fewer), found by
+        torch.topk on the device table; ties go to the lower first."""
+        if self.table is None:
+            raise ValueError("ReadDedupResult.top: the dedup was run without a table tensor")
+        import torch
+        t = self.table.reshape(-1, 3)
+        k = min(int(k), t.shape[0])
+        if k <= 0:
+            return []
+        # one score per row: the count first, then the lower record number (first < records)
+        m = self.records + 1
+        score = torch.where(t[:, 0] != 0, t[:, 2] * m + (m - 1 - t[:, 1]), torch.full_like(t[:, 2], -1))
+        rows = t[torch.topk(score, k).indices].cpu().numpy()
+        return [(int(c), int(f)) for key, f, c in rows if key != 0]
+
+    def __repr__(self):
+        return (f"ReadDedupResult(records={self.records}, participating={self.participating}, unique={self.unique}, "
+                f"bases={self.bases}, bases_unique={self.bases_unique}, max_count={self.max_count}, "
+                f"max_first={self.max_first}, duplication_rate={self.duplication_rate:.4f})")
+
+
 class SelectedRecords:
     """The records a mask selects (include/ppgpu.h "record selection"): `bytes` (uint8, the selected
     records' text back to back), `sel_off` (int64, records + 1 offsets into it), `desc` (records x 4:
@@ -1052,7 +1133,7 @@ class Shard:
     def run(self):
         hooked = getattr(self, "_seqpack", None) is not None or getattr(self, "_sq_mask", None) is not None or \
             getattr(self, "_select", None) is not None or getattr(self, "_rf", None) is not None or \
-            getattr(self, "_rt", None) is not None
+            getattr(self, "_rt", None) is not None or getattr(self, "_dd", None) is not None
         if self._on_device or hooked:
             self._torch_order()   # the caller may have rewritten comp (or the hooks' tensors) since the last run
         check(lib.ppg_shard_run(self._h), "DecompressAll")
@@ -1386,6 +1467,90 @@ class Shard:
         if lib.ppg_shard_readprofile_ready(self._h, _ptr(ch), C.byref(res), _ptr(table), table.shape[0]) != 1:
             return None
         return ReadProfileResult(res, table, ch, rp[2])
+
+    def _dedup_args(self, dedup, mask, windows, first, table, and_mask, what, nrec=None):
+        """(struct, the ctypes arguments after it up to slots, (mask, windows, first, table) tensors) of a dedup
+        call.  mask / first: True allocates one for nrec records; table: None allocates the smallest legal one."""
+        import torch
+        dev = torch.device("cuda", self.dev.device)
+        if mask is True:
+            mask = torch.zeros((nrec + 31) // 32, dtype=torch.int32, device=dev)
+        elif mask is False:
+            mask = None
+        ptr, cap, mask = _mask_arg(mask, what)
+        if and_mask and ptr is None:
+            raise ValueError(f"{what}: and_mask needs a mask tensor")
+        wptr, wcap = None, 0
+        if windows is not None:
+            if not (hasattr(windows, "data_ptr") and windows.is_cuda and windows.dtype in (torch.int32, torch.uint32)
+                    and windows.is_contiguous()):
+                raise ValueError(f"{what}: windows must be a contiguous int32 / uint32 CUDA tensor")
+            wcap = windows.numel() // 2
+            wptr = C.c_void_p(windows.data_ptr()) if wcap else None
+        if first is True:
+            first = torch.zeros(nrec, dtype=torch.int64, device=dev)
+        elif first is False:
+            first = None
+        fptr, fcap = None, 0
+        if first is not None:
+            if not (hasattr(first, "data_ptr") and first.is_cuda and first.dtype == torch.int64 and first.is_contiguous()):
+                raise ValueError(f"{what}: first must be a contiguous int64 CUDA tensor")
+            fcap = first.numel()
+            fptr = C.c_void_p(first.data_ptr()) if fcap else None
+        if table is None:
+            table = torch.zeros((ReadDedup.min_slots(nrec), 3), dtype=torch.int64, device=dev)
+        if not (hasattr(table, "data_ptr") and table.is_cuda and table.dtype == torch.int64 and table.is_contiguous()
+                and table.numel() % 3 == 0):
+            raise ValueError(f"{what}: table must be a contiguous int64 CUDA tensor of slots x 3 values")
+        d = _dedup_struct(dedup, and_mask, wptr is not None)
+        args = (ptr, cap, wptr, wcap if wptr is not None else 0, fptr, fcap if fptr is not None else 0,
+                C.c_void_p(table.data_ptr()), table.numel() // 3)
+        return d, args, (None if mask is None else mask.view(torch.uint32), windows, first, table)
+
+    def dedup_reads(self, dedup, mask=False, windows=None, first=False, table=None, and_mask=False):
+        """The read dedup `dedup` (a ReadDedup) over the records of a one-batch shard after its run
+        (ppg_shard_dedup_reads), as a ReadDedupResult.  mask=True also returns the unique bits as a uint32 CUDA
+        tensor; a tensor of hit-mask words is written instead, or with and_mask=True decides which records
+        participate and is ANDed in place with the unique bits.  windows: an int32 / uint32 CUDA tensor of
+        (start, len) rows (a trim's): the key bytes come from inside them.  first=True also returns the first
+        occurrence's record number per record.  table: an int64 CUDA tensor [slots, 3], slots a power of two of
+        at least 2 x records; None allocates the smallest legal one.  Ordered after torch's stream, complete on
+        return."""
+        nrec = max(self.total_records, 0)
+        d, args, keep = self._dedup_args(dedup, mask, windows, first, table, and_mask, "dedup_reads", nrec)
+        self._torch_order()
+        res, ch = _lib.PpgReadDedupResult(), np.zeros(self.n, np.int64)
+        check(lib.ppg_shard_dedup_reads(self._h, C.byref(d), *args, _ptr(ch), C.byref(res)), "dedup_reads")
+        return ReadDedupResult(res, ch, keep[0], keep[2], keep[3])
+
+    def set_readdedup(self, dedup, mask=None, windows=None, first=None, table=None, and_mask=False):
+        """From the next run on, every output batch is deduplicated by `dedup` against `table` while its output
+        is resident (ppg_shard_set_readdedup): works for shards of any number of batches, and runs after the
+        set_seqquery, set_readfilter and set_readtrim hooks and before the set_readprofile and set_select
+        hooks, so with and_mask=True on their mask tensor those see first occurrences only; the result is
+        `readdedup` after the run.  mask, windows, first and table as in dedup_reads, tensors sized for the
+        whole shard (table: required).  dedup=None turns it off."""
+        if dedup is None:
+            check(lib.ppg_shard_set_readdedup(self._h, None, None, 0, None, 0, None, 0, None, 0), "set_readdedup")
+            self._dd = None
+            return self
+        if table is None:
+            raise ValueError("set_readdedup: a table tensor is required (ReadDedup.min_slots(records) x 3 int64)")
+        d, args, keep = self._dedup_args(dedup, False if mask is None else mask, windows, False if first is None else first,
+                                         table, and_mask, "set_readdedup")
+        self._dd = keep   # kept alive while the library may write them
+        self._torch_order()
+        check(lib.ppg_shard_set_readdedup(self._h, C.byref(d), *args), "set_readdedup")
+        return self
+
+    @property
+    def readdedup(self):
+        """The ReadDedupResult of the last run's set_readdedup hook, or None when that run did not complete one."""
+        res, ch = _lib.PpgReadDedupResult(), np.zeros(self.n, np.int64)
+        if lib.ppg_shard_readdedup_ready(self._h, _ptr(ch), C.byref(res)) != 1:
+            return None
+        dd = getattr(self, "_dd", None) or (None, None, None, None)
+        return ReadDedupResult(res, ch, dd[0], dd[2], dd[3])
 
     def select_size(self, mask=None):
         """(records, bytes) a selection by `mask` holds, after a run of any number of batches
@@ -1921,7 +2086,8 @@ class BatchedFASTQ:
 
     def _stage_shard(self):
         """The query shard with every record-stage hook off: each Count* / Profile attaches its own."""
-        return self._query_shard().set_seqquery(None).set_readfilter(None).set_readtrim(None).set_readprofile(None)
+        sh = self._query_shard().set_seqquery(None).set_readfilter(None).set_readtrim(None).set_readprofile(None)
+        return sh.set_readdedup(None)
 
     def _query(self, pattern):
         return self._stage_shard().set_seqquery(pattern).run().seqquery
@@ -1938,23 +2104,20 @@ class BatchedFASTQ:
         alone, no record text and no window reaches the host."""
         return self._stage_shard().set_readtrim(trim).run().readtrim
 
-    def Profile(self, profile=None, pattern=None, filter=None, trim=None):   # noqa: A002
-        """The ReadProfileResult of the file: bases and qualities per read position, read lengths, GC
-        content and mean quality per read (profile: a ReadProfile, None for the default), made on the GPU
-        batch by batch (Shard.set_readprofile).  With pattern / filter / trim it is the profile of the
-        reads that contain the pattern, pass the filter and are kept by the trim, inside the trim's
-        windows: one mask tensor and one rows tensor are chained through the hooks on the device, and
-        nothing but the result leaves it."""
-        sh = self._stage_shard()
-        profile = ReadProfile() if profile is None else profile
-        if pattern is None and filter is None and trim is None:
-            return sh.set_readprofile(profile).run().readprofile
+    def _stage_records(self, sh):
+        """The file's records: one run without hooks counts them, once per query shard (the tensors' sizes)."""
+        nrec = getattr(sh, "_profile_records", None)
+        if nrec is None:
+            nrec = sh._profile_records = max(sh.run().total_records, 0)
+        return nrec
+
+    def _chain(self, sh, nrec, pattern, filter, trim, dedup):   # noqa: A002
+        """Attaches the query / filter / trim / dedup hooks that are given to one mask tensor and one rows
+        tensor; (mask, rows), each None when no stage needs it."""
         import torch
         dev = torch.device("cuda", sh.dev.device)
-        nrec = getattr(sh, "_profile_records", None)
-        if nrec is None:   # the tensors' sizes: one run without hooks counts the records
-            nrec = sh._profile_records = max(sh.run().total_records, 0)
-        mask = torch.full(((nrec + 31) // 32 + 1,), -1, dtype=torch.int32, device=dev)
+        masked = pattern is not None or filter is not None or trim is not None
+        mask = torch.full(((nrec + 31) // 32 + 1,), -1, dtype=torch.int32, device=dev) if masked or dedup is not None else None
         rows = torch.zeros((nrec + 1, 2), dtype=torch.int32, device=dev) if trim is not None else None
         if pattern is not None:
             sh.set_seqquery(pattern, mask=mask)   # writes the words; the later stages AND into them
@@ -1962,10 +2125,47 @@ class BatchedFASTQ:
             sh.set_readfilter(filter, mask=mask, and_mask=True)
         if trim is not None:
             sh.set_readtrim(trim, mask=mask, windows=rows, and_mask=True)
+        if dedup is not None:
+            table = torch.zeros((ReadDedup.min_slots(nrec), 3), dtype=torch.int64, device=dev)
+            sh.set_readdedup(dedup, mask=mask, windows=rows, table=table, and_mask=True)
+        return mask, rows
+
+    def Duplication(self, dedup=None, pattern=None, filter=None, trim=None):   # noqa: A002
+        """The ReadDedupResult of the file: how many reads are first occurrences, the duplication levels and the
+        most frequent read (dedup: a ReadDedup, None for whole reads), made on the GPU batch by batch against
+        one table in device memory (Shard.set_readdedup).  With pattern / filter / trim it is the duplication
+        among the reads that contain the pattern, pass the filter and are kept by the trim, keyed inside the
+        trim's windows.  One counting run gives the sizes; one mask, one rows tensor and one table are chained
+        through the hooks, and nothing but the result leaves the device."""
+        sh = self._stage_shard()
+        nrec = self._stage_records(sh)
         try:
+            self._chain(sh, nrec, pattern, filter, trim, ReadDedup() if dedup is None else dedup)
+            return sh.run().readdedup
+        finally:
+            self._stage_shard()
+
+    def CountUnique(self, dedup=None, pattern=None, filter=None, trim=None):   # noqa: A002
+        """The number of first occurrences Duplication() finds."""
+        return self.Duplication(dedup, pattern, filter, trim).unique
+
+    def Profile(self, profile=None, pattern=None, filter=None, trim=None, dedup=None):   # noqa: A002
+        """The ReadProfileResult of the file: bases and qualities per read position, read lengths, GC
+        content and mean quality per read (profile: a ReadProfile, None for the default), made on the GPU
+        batch by batch (Shard.set_readprofile).  With pattern / filter / trim it is the profile of the
+        reads that contain the pattern, pass the filter and are kept by the trim, inside the trim's
+        windows: one mask tensor and one rows tensor are chained through the hooks on the device, and
+        nothing but the result leaves it.  dedup (a ReadDedup): of those, the first occurrences only."""
+        sh = self._stage_shard()
+        profile = ReadProfile() if profile is None else profile
+        if pattern is None and filter is None and trim is None and dedup is None:
+            return sh.set_readprofile(profile).run().readprofile
+        nrec = self._stage_records(sh)
+        try:
+            mask, rows = self._chain(sh, nrec, pattern, filter, trim, dedup)
             return sh.set_readprofile(profile, mask=mask, windows=rows).run().readprofile
         finally:
-            sh.set_seqquery(None).set_readfilter(None).set_readtrim(None).set_readprofile(None)
+            self._stage_shard()
 
     def QualityCounts(self):
         """numpy int64[256]: the bytes of every Quality line by value, counted on the GPU batch by batch."""

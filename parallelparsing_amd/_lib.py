@@ -141,6 +141,10 @@ _SIGS = {
     "ppg_shard_profile_reads": (C.c_int, [vp, vp, vp, i64, vp, i64, vp, vp, vp, i64]),
     "ppg_shard_set_readprofile": (C.c_int, [vp, vp, vp, i64, vp, i64]),
     "ppg_shard_readprofile_ready": (C.c_int, [vp, vp, vp, vp, i64]),
+    "ppg_read_dedup_check": (C.c_int, [vp]),
+    "ppg_shard_dedup_reads": (C.c_int, [vp, vp, vp, i64, vp, i64, vp, i64, vp, i64, vp, vp]),
+    "ppg_shard_set_readdedup": (C.c_int, [vp, vp, vp, i64, vp, i64, vp, i64, vp, i64]),
+    "ppg_shard_readdedup_ready": (C.c_int, [vp, vp, vp]),
     "ppg_shard_select_size": (C.c_int, [vp, vp, i64, P(i64), P(i64)]),
     "ppg_shard_select_records": (C.c_int, [vp, vp, i64, vp, vp, vp, i64, vp, i64, P(i64), P(i64)]),
     "ppg_shard_set_select": (C.c_int, [vp, vp, i64, vp, vp, vp, i64, vp, i64]),
@@ -240,6 +244,21 @@ class PpgReadProfileResult(C.Structure):
 
 
 PPG_PROFILE_USE_MASK, PPG_PROFILE_USE_WINDOWS, PPG_PROFILE_MAX_POS = 1, 2, 1024
+
+
+class PpgReadDedup(C.Structure):
+    """ppg_read_dedup (include/ppgpu.h)."""
+    _fields_ = [("flags", C.c_int64), ("max_bases", C.c_int64), ("reserved", C.c_int64 * 2)]
+
+
+class PpgReadDedupResult(C.Structure):
+    """ppg_read_dedup_result (include/ppgpu.h)."""
+    _fields_ = [("records", C.c_int64), ("participating", C.c_int64), ("unique", C.c_int64), ("bases", C.c_int64),
+                ("bases_unique", C.c_int64), ("overflow", C.c_int64), ("max_count", C.c_int64), ("max_first", C.c_int64),
+                ("level_distinct", C.c_int64 * 16), ("level_reads", C.c_int64 * 16)]
+
+
+PPG_DEDUP_USE_WINDOWS, PPG_DEDUP_AND_MASK = 2, 0x100
 
 
 for _name, (_res, _args) in _SIGS.items():

@@ -141,6 +141,14 @@ constexpr int kRpTile(int max_pos) {
 }
 static_assert(kRpTile(256) == 256 && kRpTile(kRpMaxPos) == 192 && kRpTile(1) == 32, "ppg_rp_measure's quality rows");
 
+// a ppg_read_dedup (include/ppgpu.h "read dedup") as the dedup kernels' argument
+struct PpgReadDedup {
+    int64_t flags, max_bases, reserved[2];
+};
+// the read dedup's accumulators: the int64 fields of a ppg_read_dedup_result in order (records, participating,
+// unique, bases, bases_unique, overflow, max_count, max_first, level_distinct[16], level_reads[16])
+constexpr int kDdAcc = 40;
+
 // ppg_sel_copy: the destination bytes one workgroup writes (256 threads x 4 words of 16 B); ppg_sel_place
 // records, per multiple of it inside a batch's destination range, the selected record that holds that byte
 constexpr uint32_t kSelSpan = 16384;

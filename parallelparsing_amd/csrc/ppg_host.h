@@ -243,6 +243,22 @@ struct ProfileStage : StageOut {
     int64_t values() const { return kRpFixed + (int64_t)kRpRow * out_pos; }
 };
 
+// ppg_shard_set_readdedup: every batch's records are also deduplicated (ppg_readdedup.hip) against the table,
+// which persists across the batches of a run; the mask, the (start, len) rows and the first-occurrence row at
+// the shard record number.  acc: kDdAcc values.
+struct DedupStage : StageOut {
+    PpgReadDedup dd = {};
+    uint32_t *mask = nullptr;
+    int64_t mask_cap = 0;
+    const uint32_t *rows = nullptr;
+    int64_t rows_cap = 0;
+    int64_t *first = nullptr;
+    int64_t first_cap = 0;
+    uint64_t *table = nullptr;
+    int64_t slots = 0;
+    DevBuf<uint64_t> rsc;   // scratch: the sum of the unit hashes and the table row of one batch's records
+};
+
 // ppg_shard_set_select: every batch's selected records are also appended to these buffers
 // (ppg_seqselect.hip), output records and bytes continuing from the batches before
 struct SelectStage {
@@ -307,6 +323,7 @@ struct ppg_shard {
     QueryStage query;
     FilterStage filter;
     TrimStage trim;
+    DedupStage dedup;
     ProfileStage profile;
     SelectStage select;
     // split chunks (ppg_shard_set_split): the inflate launch runs sub-jobs, ppg_split_merge folds
@@ -356,7 +373,7 @@ bool pread_parallel(int fd, uint8_t *dst, int64_t off, int64_t len, int threads)
 // descriptor; rec0: its first record's shard record number; tot: its records.  Everything is queued on the
 // shard's stream; the calls said to block synchronise it. ----
 PpgBatchView batch_view(const ppg_shard *sh, int32_t b0, int32_t b1, const uint32_t *recs);
-// batch_collect's one call: the batch's hooks in the order keys, pack, query, filter, trim, profile, select
+// batch_collect's one call: the batch's hooks in the order keys, pack, query, filter, trim, dedup, profile, select
 int shard_batch_hooks(ppg_shard *sh, int32_t b0, int32_t b1, int64_t tot);
 // ppg_shard_run's two: no hook's output counts as written during a run; a run that succeeded wrote them all
 void stages_run_begin(ppg_shard *sh);
@@ -392,6 +409,13 @@ bool readtrim_ok(const void *trim, PpgReadTrim *out);
 // has drained.
 int shard_read_profile(ppg_shard *sh, int32_t b0, int32_t b1, const uint32_t *recs, int64_t rec0, int64_t tot,
                        const PpgReadProfile &prf, const uint32_t *mask, const uint32_t *rows, bool first);
+// read dedup, after shard_layout of the same chunks; mask, rows and first_out (all at the shard's record 0) may
+// be null; table: slots rows, made empty when `first`; last: the run's last batch, after which the levels
+// are made.  The caller has checked 2 * (rec0 + tot) <= slots.  The totals so far and the chunks' uniques are
+// in dedup.host once the stream has drained.
+int shard_read_dedup(ppg_shard *sh, int32_t b0, int32_t b1, const uint32_t *recs, int64_t rec0, int64_t tot,
+                     const PpgReadDedup &dd, uint32_t *mask, const uint32_t *rows, int64_t *first_out, uint64_t *table,
+                     int64_t slots, bool first, bool last);
 // record selection (record j of the batch has bit bit0 + j of mask, a null mask selects all).  sizes: the
 // selected records and their bytes (blocks).  move: after sizes of the same chunks, queues the selection into
 // the buffers from output record rec_lo and byte byte_lo on; recno counts from bit0.

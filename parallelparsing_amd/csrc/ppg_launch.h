@@ -118,6 +118,23 @@ PPG_WEAK hipError_t ppg_launch_rp_finish(hipStream_t s, const PpgBatchView &v, c
                                          uint64_t rec0, uint64_t *acc, int64_t *host_chunk_profiled);
 PPG_WEAK hipError_t ppg_launch_rp_totals(hipStream_t s, const uint64_t *acc, int64_t *host_result, uint32_t n);
 
+// ---- ppg_readdedup.hip ----
+// Weak for the same reason (readdedup_linked, ppg_stages.cpp).  table: slots rows of {key, first, count}.
+PPG_WEAK hipError_t ppg_launch_dd_init(hipStream_t s, uint64_t *table, uint64_t slots);
+PPG_WEAK hipError_t ppg_launch_dd_measure(hipStream_t s, const PpgBatchView &v, const uint64_t *cbase,
+                                          const int64_t *seq_off, const uint32_t *seq_len, uint64_t total,
+                                          const PpgReadDedup *dd, const uint32_t *words, const uint32_t *rows,
+                                          uint64_t rec0, uint64_t *rsc);
+PPG_WEAK hipError_t ppg_launch_dd_insert(hipStream_t s, const PpgBatchView &v, const PpgReadDedup *dd,
+                                         const uint32_t *words, const uint32_t *rows, uint64_t rec0, uint64_t *rsc,
+                                         uint64_t *table, uint64_t slots, uint64_t *acc);
+PPG_WEAK hipError_t ppg_launch_dd_decide(hipStream_t s, const PpgBatchView &v, const PpgReadDedup *dd,
+                                         const uint32_t *rows, uint64_t rec0, const uint64_t *rsc, const uint64_t *table,
+                                         uint32_t *words_out, int64_t *first_out, uint64_t *acc,
+                                         int64_t *host_chunk_unique);
+PPG_WEAK hipError_t ppg_launch_dd_levels(hipStream_t s, const uint64_t *table, uint64_t slots, uint64_t *acc);
+PPG_WEAK hipError_t ppg_launch_dd_totals(hipStream_t s, const uint64_t *acc, int64_t *host_result);
+
 // ---- ppg_seqselect.hip ----
 // Weak for the same reason (select_linked, ppg_stages.cpp).
 PPG_WEAK hipError_t ppg_launch_sel_count(hipStream_t s, const PpgBatchView &v, const uint32_t *mask, uint64_t bit0,

@@ -1,8 +1,8 @@
 // ppg_seqload.h — device helpers shared by the record-stage kernels: the lookup of a 32-base unit's chunk
 // and record and the loads of up to 32 bytes of raw_k = offset_k ++ body_k, for the kernels that read record
 // slices of a resident batch per unit (ppg_seqpack.hip, ppg_seqquery.hip, ppg_readfilter.hip,
-// ppg_readtrim.hip, ppg_readprofile.hip); is_acgt (ppg_seqpack.hip, ppg_readfilter.hip); wave_sum64
-// (ppg_readfilter.hip, ppg_readtrim.hip, ppg_readprofile.hip, ppg_seqselect.hip).
+// ppg_readtrim.hip, ppg_readprofile.hip, ppg_readdedup.hip); is_acgt (ppg_seqpack.hip, ppg_readfilter.hip);
+// wave_sum64 (ppg_readfilter.hip, ppg_readtrim.hip, ppg_readprofile.hip, ppg_readdedup.hip, ppg_seqselect.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

@@ -1,12 +1,12 @@
 // ppg_stages.cpp — the record stages of libppgpu.so: work on a batch of a shard while its output is resident
 // on the GPU.  Packed reads (ppg_seqpack.hip), sequence query (ppg_seqquery.hip), read filter
-// (ppg_readfilter.hip), read trim (ppg_readtrim.hip), read profile (ppg_readprofile.hip) and record selection
-// (ppg_seqselect.hip): for each its
+// (ppg_readfilter.hip), read trim (ppg_readtrim.hip), read dedup (ppg_readdedup.hip), read profile
+// (ppg_readprofile.hip) and record selection (ppg_seqselect.hip): for each its
 // pieces on one batch, its C entry points (one-shot on a one-batch shard, the hook of every batch of a
 // run, and what the last run left) and the measurement hook of its tools/*_probe.py.
 //
 // A batch's hooks run from one place, shard_batch_hooks, called once by batch_collect (ppg_api.cpp).  The
-// unit kernels of query, filter, trim and profile read one layout of the batch (StageLayout, ppg_host.h), which
+// unit kernels of query, filter, trim, dedup and profile read one layout of the batch (StageLayout, ppg_host.h), which
 // their caller makes with shard_layout once per batch before the first of them.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -22,7 +22,8 @@
 // the result structs are the kernels' accumulators in order; the chunk counts follow them in pinned memory
 static_assert(sizeof(ppg_seq_query_result) == 8 * 8 && sizeof(ppg_read_filter_result) == 8 * kRfAcc &&
                   sizeof(ppg_read_trim_result) == 8 * kRtAcc && sizeof(ppg_read_profile_result) == 8 * kRpFixed &&
-                  sizeof(ppg_read_profile) == sizeof(PpgReadProfile) && PPG_PROFILE_MAX_POS == kRpMaxPos,
+                  sizeof(ppg_read_profile) == sizeof(PpgReadProfile) && PPG_PROFILE_MAX_POS == kRpMaxPos &&
+                  sizeof(ppg_read_dedup_result) == 8 * kDdAcc && sizeof(ppg_read_dedup) == sizeof(PpgReadDedup),
               "a stage's result struct is its accumulators");
 
 static bool seq_linked() {   // (weak references, ppg_launch.h: absent from the host-only sanitizer build)
@@ -43,6 +44,11 @@ static bool readtrim_linked() {
 
 static bool readprofile_linked() {
     return seq_linked() && ppg_launch_rp_measure && ppg_launch_rp_finish && ppg_launch_rp_totals;
+}
+
+static bool readdedup_linked() {
+    return seq_linked() && ppg_launch_dd_init && ppg_launch_dd_measure && ppg_launch_dd_insert && ppg_launch_dd_decide &&
+           ppg_launch_dd_levels && ppg_launch_dd_totals;
 }
 
 static bool select_linked() {
@@ -320,6 +326,69 @@ static void readprofile_outputs(const ProfileStage &p, int32_t n, int64_t P, int
     if (chunk_profiled && n) memcpy(chunk_profiled, p.host.p + fixed + rows, 8 * (size_t)n);
 }
 
+// ---- read dedup (ppg_readdedup.hip) ----
+// the rules of include/ppgpu.h "read dedup"; host only
+static bool readdedup_ok(const void *dedup, PpgReadDedup *out) {
+    if (!dedup) return false;
+    PpgReadDedup d;
+    memcpy(&d, dedup, sizeof d);
+    if (d.flags & ~(int64_t)(PPG_DEDUP_USE_WINDOWS | PPG_DEDUP_AND_MASK)) return false;
+    if (d.max_bases < 0 || d.reserved[0] != 0 || d.reserved[1] != 0) return false;
+    if (out) *out = d;
+    return true;
+}
+
+// AND_MASK with its mask, the windows with their flag and the flag with its windows, the table
+static bool readdedup_bufs_ok(const PpgReadDedup &d, const uint32_t *mask, int64_t mask_cap, const void *rows,
+                              int64_t rows_cap, const int64_t *first, int64_t first_cap, const uint64_t *table,
+                              int64_t slots) {
+    if (!seqquery_mask_ok(mask, mask_cap) || ((d.flags & PPG_DEDUP_AND_MASK) && !mask)) return false;
+    if (((d.flags & PPG_DEDUP_USE_WINDOWS) != 0) != (rows != nullptr)) return false;
+    if (rows_cap < 0 || ((uintptr_t)rows & 7) != 0 || (!rows && rows_cap != 0)) return false;
+    if (first_cap < 0 || ((uintptr_t)first & 7) != 0 || (!first && first_cap != 0)) return false;
+    return table && ((uintptr_t)table & 7) == 0 && slots >= 64 && (slots & (slots - 1)) == 0;
+}
+
+// a cap or the table's load of 1/2 that `after` records of the run would exceed
+static bool readdedup_full(const uint32_t *mask, int64_t mask_cap, const void *rows, int64_t rows_cap, const int64_t *first,
+                           int64_t first_cap, int64_t slots, int64_t after) {
+    return (mask && after > mask_cap) || (rows && after > rows_cap) || (first && after > first_cap) || after > slots / 2;
+}
+
+int shard_read_dedup(ppg_shard *sh, int32_t b0, int32_t b1, const uint32_t *recs, int64_t rec0, int64_t tot,
+                     const PpgReadDedup &dd, uint32_t *mask, const uint32_t *rows, int64_t *first_out, uint64_t *table,
+                     int64_t slots, bool first, bool last) {
+    hipStream_t s = shard_stream(sh);
+    const PpgBatchView v = batch_view(sh, b0, b1, recs);
+    DedupStage &d = sh->dedup;
+    if (!readdedup_linked()) return PPG_UNSUPPORTED;
+    const bool and_mask = (dd.flags & PPG_DEDUP_AND_MASK) != 0;
+    HIPCHK(grow_buf(d.rsc, 2 * ((size_t)tot + 1)));
+    if (int rc = stage_out_begin(sh, d, kDdAcc, first)) return rc;
+    if (first) HIPCHK(ppg_launch_dd_init(s, table, (uint64_t)slots));
+    if (tot) HIPCHK(hipMemsetAsync(d.rsc.p, 0, 16 * (size_t)tot, s));
+    // as the filter: this batch's words; AND_MASK changes its bits alone
+    if (mask && !and_mask) HIPCHK(clear_batch_words(s, mask, (uint64_t)rec0, (uint64_t)tot));
+    const uint32_t *part = and_mask ? mask : nullptr;   // the bits that decide participation
+    HIPCHK(ppg_launch_dd_measure(s, v, sh->lay.cbase.p, sh->lay.off.p, sh->lay.len.p, (uint64_t)sh->lay.total, &dd, part, rows,
+                                 (uint64_t)rec0, d.rsc.p));
+    HIPCHK(ppg_launch_dd_insert(s, v, &dd, part, rows, (uint64_t)rec0, d.rsc.p, table, (uint64_t)slots, d.acc.p));
+    HIPCHK(ppg_launch_dd_decide(s, v, &dd, rows, (uint64_t)rec0, d.rsc.p, table, mask, first_out, d.acc.p,
+                                d.result() + kDdAcc + b0));
+    if (last) {   // the levels and the greatest row, once: max_first starts from "none"
+        HIPCHK(hipMemsetAsync(d.acc.p + 7, 0xFF, 8, s));
+        HIPCHK(ppg_launch_dd_levels(s, table, (uint64_t)slots, d.acc.p));
+    }
+    HIPCHK(ppg_launch_dd_totals(s, d.acc.p, d.result()));
+    return PPG_OK;
+}
+
+// what the last completed dedup left in pinned memory (n: the shard's chunks)
+static void readdedup_outputs(const DedupStage &d, int32_t n, int64_t *chunk_unique, void *result) {
+    d.outputs(n, chunk_unique, result, sizeof(ppg_read_dedup_result));
+    if (!d.host.p && result) ((ppg_read_dedup_result *)result)->max_first = -1;   // no batch ran: an empty table
+}
+
 // ---- record selection (ppg_seqselect.hip) ----
 int shard_select_reserve(ppg_shard *sh, int64_t nchunks) {
     HIPCHK(sh->select.ccnt.alloc(2 * ((size_t)nchunks + 1)));
@@ -381,11 +450,12 @@ static int select_hook(ppg_shard *sh, int32_t b0, int32_t b1, const uint32_t *re
 
 // ---- a batch's hooks ----
 // Everything attached to the shard, on the batch [b0, b1) of tot records that batch_collect has just waited
-// for, in the order keys, pack, query, filter, trim, profile, select.  The batch's output is resident: the
+// for, in the order keys, pack, query, filter, trim, dedup, profile, select.  The batch's output is resident: the
 // next batch's inflate follows on the same stream, so it is read before it is overwritten.  A filter with
-// AND_MASK on the query's mask sees this batch's hit bits, a trim what both have left of them, the profile
-// reads the mask and the rows as the trim left them, and the selection, last, hands over the product.  A cap
-// that the batch would exceed fails with PPG_BUF_ERROR before the stage writes anything.
+// AND_MASK on the query's mask sees this batch's hit bits, a trim what both have left of them, a dedup with
+// AND_MASK clears all but the first occurrences among those (its table persists from batch to batch), the
+// profile reads the mask and the rows as they were left, and the selection, last, hands over the product.  A
+// cap that the batch would exceed fails with PPG_BUF_ERROR before the stage writes anything.
 int shard_batch_hooks(ppg_shard *sh, int32_t b0, int32_t b1, int64_t tot) {
     const int64_t rec0 = sh->total_records, after = rec0 + tot;
     const uint32_t *recs = sh->recs.p + 4 * (uint64_t)rec0;
@@ -405,11 +475,14 @@ int shard_batch_hooks(ppg_shard *sh, int32_t b0, int32_t b1, int64_t tot) {
     const QueryStage &q = sh->query;
     const FilterStage &f = sh->filter;
     const TrimStage &t = sh->trim;
+    const DedupStage &d = sh->dedup;
     const ProfileStage &p = sh->profile;
-    if (q.on || f.on || t.on || p.on) {   // the unit kernels' layout, once for the four
+    if (q.on || f.on || t.on || d.on || p.on) {   // the unit kernels' layout, once for the five
         if (q.on && q.mask && after > q.rec_cap) return PPG_BUF_ERROR;
         if (f.on && ((f.mask && after > f.rec_cap) || (f.metrics && after > f.metrics_cap))) return PPG_BUF_ERROR;
         if (t.on && ((t.mask && after > t.rec_cap) || (t.rows && after > t.rows_cap))) return PPG_BUF_ERROR;
+        if (d.on && readdedup_full(d.mask, d.mask_cap, d.rows, d.rows_cap, d.first, d.first_cap, d.slots, after))
+            return PPG_BUF_ERROR;
         if (p.on && ((p.mask && after > p.mask_cap) || (p.rows && after > p.rows_cap))) return PPG_BUF_ERROR;
         if (int rc = shard_layout(sh, b0, b1, recs, tot)) return rc;
     }
@@ -419,6 +492,10 @@ int shard_batch_hooks(ppg_shard *sh, int32_t b0, int32_t b1, int64_t tot) {
         if (int rc = shard_read_filter(sh, b0, b1, recs, rec0, tot, f.flt, f.mask, f.metrics, first)) return rc;
     if (t.on)
         if (int rc = shard_read_trim(sh, b0, b1, recs, rec0, tot, t.trm, t.mask, t.rows, first)) return rc;
+    if (d.on)
+        if (int rc = shard_read_dedup(sh, b0, b1, recs, rec0, tot, d.dd, d.mask, d.rows, d.first, d.table, d.slots, first,
+                                      b1 == sh->n))
+            return rc;
     if (p.on)
         if (int rc = shard_read_profile(sh, b0, b1, recs, rec0, tot, p.prf, p.mask, p.rows, first)) return rc;
     if (sh->select.on)
@@ -428,7 +505,7 @@ int shard_batch_hooks(ppg_shard *sh, int32_t b0, int32_t b1, int64_t tot) {
 
 void stages_run_begin(ppg_shard *sh) {
     sh->keys_written = sh->pack.written = sh->query.written = sh->filter.written = sh->trim.written = sh->profile.written = 0;
-    sh->select.written = 0;
+    sh->dedup.written = sh->select.written = 0;
 }
 
 void stages_run_end(ppg_shard *sh, bool ok) {
@@ -437,6 +514,7 @@ void stages_run_end(ppg_shard *sh, bool ok) {
     sh->query.written = ok && sh->query.on;
     sh->filter.written = ok && sh->filter.on;
     sh->trim.written = ok && sh->trim.on;
+    sh->dedup.written = ok && sh->dedup.on;
     sh->profile.written = ok && sh->profile.on;
     sh->select.written = ok && sh->select.on;
 }
@@ -749,6 +827,62 @@ int ppg_shard_readprofile_ready(ppg_shard *sh, int64_t *chunk_profiled, void *re
     if (!p.written) return 0;
     if (table && table_cap < p.prf.max_pos) return PPG_BUF_ERROR;
     readprofile_outputs(p, sh->n, p.prf.max_pos, chunk_profiled, result, table);
+    return 1;
+}
+
+// ---- read dedup: the read trimming entry points' counterparts ----
+int ppg_read_dedup_check(const void *dedup) { return readdedup_ok(dedup, nullptr) ? PPG_OK : PPG_ARG_ERROR; }
+
+int ppg_shard_dedup_reads(ppg_shard *sh, const void *dedup, uint32_t *dev_unique_mask, int64_t mask_cap,
+                          const void *dev_windows, int64_t windows_cap, int64_t *dev_first, int64_t first_cap,
+                          void *dev_table, int64_t slots, int64_t *chunk_unique, void *result) {
+    PpgReadDedup dd;
+    if (!sh || !sh->ran || sh->batches.size() != 1 || !readdedup_ok(dedup, &dd) ||
+        !readdedup_bufs_ok(dd, dev_unique_mask, mask_cap, dev_windows, windows_cap, dev_first, first_cap,
+                           (const uint64_t *)dev_table, slots))
+        return PPG_ARG_ERROR;
+    if (!readdedup_linked()) return PPG_UNSUPPORTED;
+    if (readdedup_full(dev_unique_mask, mask_cap, dev_windows, windows_cap, dev_first, first_cap, slots, sh->total_records))
+        return PPG_BUF_ERROR;
+    HIPCHK(hipSetDevice(sh->ctx->device));
+    sh->dedup.written = 0;   // the pinned outputs are rewritten: an earlier run's hook result is gone
+    if (int rc = shard_layout(sh, 0, sh->n, sh->recs.p, sh->total_records)) return rc;
+    if (int rc = shard_read_dedup(sh, 0, sh->n, sh->recs.p, 0, sh->total_records, dd, dev_unique_mask,
+                                  (const uint32_t *)dev_windows, dev_first, (uint64_t *)dev_table, slots, true, true))
+        return rc;
+    HIPCHK(hipStreamSynchronize(shard_stream(sh)));
+    readdedup_outputs(sh->dedup, sh->n, chunk_unique, result);
+    return PPG_OK;
+}
+
+int ppg_shard_set_readdedup(ppg_shard *sh, const void *dedup, uint32_t *dev_unique_mask, int64_t mask_cap,
+                            const void *dev_windows, int64_t windows_cap, int64_t *dev_first, int64_t first_cap,
+                            void *dev_table, int64_t slots) {
+    if (!sh) return PPG_ARG_ERROR;
+    PpgReadDedup dd = {};
+    if (dedup && (!readdedup_ok(dedup, &dd) ||
+                  !readdedup_bufs_ok(dd, dev_unique_mask, mask_cap, dev_windows, windows_cap, dev_first, first_cap,
+                                     (const uint64_t *)dev_table, slots)))
+        return PPG_ARG_ERROR;
+    DedupStage &d = sh->dedup;
+    d.on = dedup ? 1 : 0;
+    d.dd = dd;
+    d.mask = dedup ? dev_unique_mask : nullptr;
+    d.mask_cap = dedup ? mask_cap : 0;
+    d.rows = dedup ? (const uint32_t *)dev_windows : nullptr;
+    d.rows_cap = dedup ? windows_cap : 0;
+    d.first = dedup ? dev_first : nullptr;
+    d.first_cap = dedup ? first_cap : 0;
+    d.table = dedup ? (uint64_t *)dev_table : nullptr;
+    d.slots = dedup ? slots : 0;
+    d.written = 0;   // completed by the next run, not by an earlier one
+    return PPG_OK;
+}
+
+int ppg_shard_readdedup_ready(ppg_shard *sh, int64_t *chunk_unique, void *result) {
+    if (!sh) return PPG_ARG_ERROR;
+    if (!sh->dedup.written) return 0;
+    readdedup_outputs(sh->dedup, sh->n, chunk_unique, result);
     return 1;
 }
 
@@ -1078,6 +1212,51 @@ int ppgx_readprofile_times(ppg_shard *sh, const void *profile, const uint32_t *d
             default:
                 e = ppg_launch_rp_finish(s, v, p.rsc.p, &prf, dev_mask, rows, 0, p.acc.p, p.result() + p.values());
                 return e != hipSuccess ? e : ppg_launch_rp_totals(s, p.acc.p, p.result(), (uint32_t)p.values());
+        }
+    });
+}
+
+// tools/readdedup_probe.py.  ms[0..4]: the layout, the measure kernel with the zeroing of its scratch, the
+// insert kernel into a table made empty first, the decide kernel + the totals' store, and the levels; windows as
+// ppg_shard_dedup_reads takes them, the table the caller's.  No mask: every record participates.
+int ppgx_readdedup_times(ppg_shard *sh, const void *dedup, const void *dev_windows, int64_t windows_cap, void *dev_table,
+                         int64_t slots, int reps, float *ms) {
+    PpgReadDedup dd;
+    if (!sh || !sh->ran || sh->batches.size() != 1 || !ms || reps < 1 || !readdedup_ok(dedup, &dd) ||
+        (dd.flags & PPG_DEDUP_AND_MASK) ||
+        !readdedup_bufs_ok(dd, nullptr, 0, dev_windows, windows_cap, nullptr, 0, (const uint64_t *)dev_table, slots) ||
+        readdedup_full(nullptr, 0, dev_windows, windows_cap, nullptr, 0, slots, sh->total_records))
+        return PPG_ARG_ERROR;
+    HIPCHK(hipSetDevice(sh->ctx->device));
+    hipStream_t s = shard_stream(sh);
+    const int64_t tot = sh->total_records;
+    const uint32_t *rows = (const uint32_t *)dev_windows;
+    uint64_t *table = (uint64_t *)dev_table;
+    DedupStage &d = sh->dedup;
+    d.written = 0;
+    if (int rc = shard_layout(sh, 0, sh->n, sh->recs.p, tot)) return rc;
+    if (int rc = shard_read_dedup(sh, 0, sh->n, sh->recs.p, 0, tot, dd, nullptr, rows, nullptr, table, slots, true, true)) return rc;
+    HIPCHK(hipStreamSynchronize(s));
+    const StageLayout &lay = sh->lay;
+    const PpgBatchView v = whole_view(sh);
+    return time_steps(s, 5, reps, ms, [&](int step) {
+        hipError_t e = hipSuccess;
+        switch (step) {
+            case 0:
+                e = launch_totals_scan(sh, s);
+                return e != hipSuccess ? e : launch_offsets(sh, s, lay.off.p, lay.len.p);
+            case 1:
+                if (tot) e = hipMemsetAsync(d.rsc.p, 0, 16 * (size_t)tot, s);
+                if (e != hipSuccess) return e;
+                return ppg_launch_dd_measure(s, v, lay.cbase.p, lay.off.p, lay.len.p, (uint64_t)lay.total, &dd, nullptr, rows, 0,
+                                             d.rsc.p);
+            case 2:
+                e = ppg_launch_dd_init(s, table, (uint64_t)slots);
+                return e != hipSuccess ? e : ppg_launch_dd_insert(s, v, &dd, nullptr, rows, 0, d.rsc.p, table, (uint64_t)slots, d.acc.p);
+            case 3:
+                e = ppg_launch_dd_decide(s, v, &dd, rows, 0, d.rsc.p, table, nullptr, nullptr, d.acc.p, d.result() + kDdAcc);
+                return e != hipSuccess ? e : ppg_launch_dd_totals(s, d.acc.p, d.result());
+            default: return ppg_launch_dd_levels(s, table, (uint64_t)slots, d.acc.p);
         }
     });
 }

@@ -34,6 +34,8 @@
 #                               -> profiles/readtrim_probe.json + readtrim_probe.log
 #   readprofile[:args]          tools/readprofile_probe.py: read profile kernels against ppg_rf_measure and ppg_seq_query,
 #                               Profile() against CountPassing -> profiles/readprofile_probe.json + readprofile_probe.log
+#   readdedup[:args]            tools/readdedup_probe.py: read dedup kernels (distinct, copy-heavy, one hot key) against
+#                               ppg_rf_measure, Duplication() against CountPassing -> profiles/readdedup_probe.json + readdedup_probe.log
 set -o pipefail
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT" || exit 1
 tag=$1; shift
@@ -139,6 +141,11 @@ run_step() {
       > $O/readprofile_probe.out 2> $O/readprofile_probe.log || { tail -5 $O/readprofile_probe.log; return 1; }
     cp profiles/readprofile_probe.json $O/
     python3 -c "import json,sys; d=json.load(open(sys.argv[1])); print(json.dumps(d['kernels'])[:2500]); print(d['file']); print({k: (round(v['records_per_s']/1e6,1), v['bytes_to_host']) for k, v in d['from_file'].items()})" $O/readprofile_probe.json ;;
+  readdedup)
+    timeout -k 10 500 python3 -u tools/readdedup_probe.py $xa \
+      > $O/readdedup_probe.out 2> $O/readdedup_probe.log || { tail -5 $O/readdedup_probe.log; return 1; }
+    cp profiles/readdedup_probe.json $O/
+    python3 -c "import json,sys; d=json.load(open(sys.argv[1])); print(json.dumps(d['kernels'])[:2500]); print({k: (round(v['records_per_s']/1e6,1), v['bytes_to_host']) for k, v in d['from_file'].items()})" $O/readdedup_probe.json ;;
   *)
     echo "gpu_run.sh: unknown step $step" >&2; return 2 ;;
   esac
