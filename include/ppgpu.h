@@ -963,6 +963,89 @@ int ppg_pairs_copy_chunk(ppg_pairs *p, int64_t j, int32_t file, uint8_t *dst, in
                          int64_t desc_cap, int64_t *nrec);
 int ppg_pairs_emit_stats(const ppg_pairs *p, double *vals, int32_t n);
 
+/* ---- pair overlap: the insert size of every pair, and the 3' cut of both mates that it gives ----
+ * The defining step of fastp on pairs: read 1 is aligned against the reverse complement of read 2 without
+ * insertions or deletions.  The alignment gives the fragment's insert size and the insert-size
+ * distribution; when the fragment is shorter than a read it gives the exact 3' cut of both mates, which is
+ * adapter trimming without knowing the adapter ("read trimming" above needs its bytes).  It works on two
+ * packed read sets ("packed reads" above; without qualities ~72 B per 150 bp record, so both files stay
+ * resident when their texts cannot), and its cut is the trim's row format: the dedup and profile hooks of
+ * each file's shard take it as it is.
+ * Inputs.  Set 1 and set 2 are packed read sets, each passed as a ppg_packed_view of device pointers (below);
+ * qual may be NULL and is not read.  Pair i < npairs is record rec1[i] of set 1 and record rec2[i] of set 2;
+ * dev_rec1 / dev_rec2 are optional device int64 arrays, 8-byte aligned.  NULL is the identity map; npairs
+ * must then not exceed that set's records (PPG_ARG_ERROR).  An entry < 0 or >= the set's records makes the
+ * pair unmapped (ppg_pairs_records gives -1 for another rank's record); no entry makes a kernel read outside
+ * the planes.  A map must not name a record twice: that record's windows row is unspecified then.
+ * Parameters.  A ppg_pair_overlap: eight int64_t, 64 bytes, passed as const void *.  flags 0; min_overlap
+ * >= 1; max_diff >= 0; max_err_milli 0 .. 1000; reserved 0.  ppg_pair_overlap_check is host only:
+ * PPG_ARG_ERROR for a NULL struct or a field outside these ranges, PPG_OK otherwise; every entry point
+ * applies it.  fastp's values are min_overlap 30, max_diff 5, max_err_milli 200.
+ * Alignment, in signed 64-bit integers.  L1 and L2 are the two reads' seq_len.  A pair with L1 or L2 above
+ * PPG_OVERLAP_MAX_LEN = 1024 is long and is not analysed.  Otherwise c1(i) is the 2-bit code of base i of
+ * read 1 and n1(i) its mask bit, c2 and n2 those of read 2.  The reverse complement R of read 2 has
+ *   cR(t) = 3 - c2(L2 - 1 - t),  nR(t) = n2(L2 - 1 - t).
+ * For an integer d with -L2 < d < L1, read-1 position i faces R position i - d.  The overlap is the i in
+ * [max(0, d), min(L1, L2 + d)) and ov(d) its length.  mis(d) counts the i of the overlap where n1(i) or
+ * nR(i - d) is set or c1(i) != cR(i - d): an N on either side is a mismatch, as in the trim.  d is accepted
+ * when ov(d) >= min_overlap, mis(d) <= max_diff and 1000 * mis(d) <= max_err_milli * ov(d).  The candidates
+ * are tried in the order d = 0, 1, ..., L1 - 1, -1, -2, ..., -(L2 - 1) -- fastp's: no adapter first, the
+ * longest overlap first -- and the first accepted one wins.  A pair with an accepted d is found; its insert
+ * size is I = L2 + d >= 1.
+ * Outputs, all optional, each a function of the planes, the maps, the struct and the rows before alone.
+ *   dev_rows        device memory, 16-byte aligned, row_cap rows of four int32: row i = (d, ov(d), mis(d), I)
+ *                   for a found pair and (0, 0, 0, 0) for every other; all npairs rows are written.
+ *   dev_found_mask  the hit-mask format, indexed by pair: every word below ceil(npairs / 32) is written
+ *                   whole, pad bits 0, nothing at or past mask_cap / 32.
+ *   dev_windows1, dev_windows2  the trim's row format (two uint32 (start, len), 8-byte aligned, win_cap1 /
+ *                   win_cap2 rows), indexed by the record number in their set, so each file's shard hooks
+ *                   read them directly.  Read, clipped and written for the two records of a found pair
+ *                   only: with the row (s, n) and that read's length L, s' = min(s, L), n' = min(n, L - s'),
+ *                   e = min(s' + n', I); the new row is (s', e - s') if e > s', else (0, 0).  No other row
+ *                   changes.  A caller without a trim starts from rows (0, seq_len).
+ *   result          a host ppg_pair_overlap_result, declared below.
+ *   hist            host int64, hist_cap >= PPG_OVERLAP_HIST = 2048 bins: hist[I] counts the found pairs;
+ *                   the first 2048 bins are written.
+ * PPG_BUF_ERROR, nothing written: npairs above row_cap (with rows) or mask_cap (with a mask), a set's records
+ * above its win_cap (with that plane), hist_cap below 2048 (with hist).  PPG_ARG_ERROR: a NULL ctx, view or
+ * view plane other than qual, a negative count or cap, a misaligned pointer, a mask_cap that is no multiple of
+ * 32.  The call runs on the ctx stream and blocks, like the other one-shot calls; the caller orders the
+ * producers of the planes before it with ppg_ctx_wait_stream. */
+enum { PPG_OVERLAP_MAX_LEN = 1024, PPG_OVERLAP_HIST = 2048 };
+typedef struct {
+    const int64_t *seq_off;  /* records + 1 entries */
+    const uint32_t *seq_len;
+    const uint32_t *bases;
+    const uint32_t *mask;
+    const uint8_t *qual;     /* may be NULL; not read */
+    int64_t records;
+} ppg_packed_view;
+typedef struct {
+    int64_t flags;           /* 0 */
+    int64_t min_overlap;     /* the least overlap that counts */
+    int64_t max_diff;        /* the most mismatches in it */
+    int64_t max_err_milli;   /* ... and 1000 x their largest fraction */
+    int64_t reserved[4];     /* 0 */
+} ppg_pair_overlap;
+typedef struct {
+    int64_t pairs;           /* pairs given */
+    int64_t unmapped;
+    int64_t too_long;        /* long pairs */
+    int64_t analysed;
+    int64_t found;
+    int64_t negative;        /* found with d < 0 */
+    int64_t adapter;         /* found with I < L1 or I < L2 */
+    int64_t overlap_bases;   /* sum of ov over the found pairs */
+    int64_t mismatches;      /* sum of mis */
+    int64_t clipped[2];      /* sum over the found pairs of max(L - I, 0), per mate */
+    int64_t reserved[5];
+} ppg_pair_overlap_result;
+int ppg_pair_overlap_check(const void *overlap);
+int ppg_pairs_overlap(ppg_ctx *ctx, const void *overlap, const void *set1, const void *set2, const int64_t *dev_rec1,
+                      const int64_t *dev_rec2, int64_t npairs, void *dev_rows, int64_t row_cap,
+                      uint32_t *dev_found_mask, int64_t mask_cap, void *dev_windows1, int64_t win_cap1,
+                      void *dev_windows2, int64_t win_cap2, void *result, int64_t *hist, int64_t hist_cap);
+
 /* Library build string (kernel ISA, version). */
 const char *ppg_version(void);
 /* "inflate-<16 hex>": a hash of the inflate kernels' object (all variants + launcher), fixed at

@@ -170,6 +170,44 @@ public unsafe struct PpgReadDedupResult  // ppg_read_dedup_result
     public fixed long LevelReads[16];
 }
 
+[StructLayout(LayoutKind.Sequential)]
+public unsafe struct PpgPackedView      // ppg_packed_view: device pointers of a packed read set
+{
+    public long* SeqOff;                // records + 1 entries
+    public uint* SeqLen;
+    public uint* Bases;
+    public uint* Mask;
+    public byte* Qual;                  // may be null; the overlap does not read it
+    public long Records;
+}
+
+[StructLayout(LayoutKind.Sequential)]
+public unsafe struct PpgPairOverlap     // ppg_pair_overlap
+{
+    public long Flags;                  // 0
+    public long MinOverlap;             // fastp: 30
+    public long MaxDiff;                // fastp: 5
+    public long MaxErrMilli;            // fastp: 200
+    public fixed long Reserved[4];      // 0
+}
+
+[StructLayout(LayoutKind.Sequential)]
+public unsafe struct PpgPairOverlapResult  // ppg_pair_overlap_result
+{
+    public const int MaxLen = 1024, HistBins = 2048;   // PPG_OVERLAP_MAX_LEN, PPG_OVERLAP_HIST
+    public long Pairs;
+    public long Unmapped;
+    public long TooLong;
+    public long Analysed;
+    public long Found;
+    public long Negative;               // found with d < 0
+    public long Adapter;                // found with an insert shorter than a mate
+    public long OverlapBases;
+    public long Mismatches;
+    public fixed long Clipped[2];       // bases cut from R1 / R2
+    public fixed long Reserved[5];
+}
+
 internal static unsafe class PpGpu
 {
     const string Lib = "ppgpu";   // libppgpu.so from parallelparsing_amd/
@@ -373,6 +411,14 @@ internal static unsafe class PpGpu
     [DllImport(Lib)] public static extern int ppg_pairs_copy_chunk(nint pairs, long j, int file, byte* dst, long cap,
         out long len, uint* desc, long descCap, out long nrec);
     [DllImport(Lib)] public static extern int ppg_pairs_emit_stats(nint pairs, double* vals, int n);
+
+    // pair overlap: insert sizes and the 3' cut of both mates (overlap: a PpgPairOverlap*, set1 / set2: a
+    // PpgPackedView*, result: a PpgPairOverlapResult*; the maps, rows, mask and windows are device pointers,
+    // hist is host memory of PpgPairOverlapResult.HistBins longs)
+    [DllImport(Lib)] public static extern int ppg_pair_overlap_check(void* overlap);
+    [DllImport(Lib)] public static extern int ppg_pairs_overlap(nint ctx, void* overlap, void* set1, void* set2,
+        long* devRec1, long* devRec2, long npairs, void* devRows, long rowCap, uint* devFoundMask, long maskCap,
+        void* devWindows1, long winCap1, void* devWindows2, long winCap2, void* result, long* hist, long histCap);
 
     [DllImport(Lib)] public static extern nint ppg_version();
     [DllImport(Lib)] public static extern nint ppg_build_id();

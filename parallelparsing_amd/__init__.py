@@ -974,6 +974,122 @@ class ReadDedupResult:
                 f"max_first={self.max_first}, duplication_rate={self.duplication_rate:.4f})")
 
 
+class PairOverlap:
+    """A pair overlap (include/ppgpu.h "pair overlap"): read 1 against the reverse complement of read 2, an
+    offset accepted with at least min_overlap bases of overlap, at most max_diff mismatches and at most
+    max_err_milli / 1000 of the overlap mismatching.  The defaults are fastp's."""
+
+    def __init__(self, min_overlap=30, max_diff=5, max_err_milli=200):
+        self.min_overlap, self.max_diff, self.max_err_milli = min_overlap, max_diff, max_err_milli
+
+    def struct(self):
+        """The ppg_pair_overlap of this overlap; ValueError when ppg_pair_overlap_check refuses it."""
+        o = _lib.PpgPairOverlap(0, int(self.min_overlap), int(self.max_diff), int(self.max_err_milli), (C.c_int64 * 4)())
+        if lib.ppg_pair_overlap_check(C.byref(o)) != 0:
+            raise ValueError(f"PairOverlap: not a valid overlap: {self!r}")
+        return o
+
+    def __repr__(self):
+        return f"PairOverlap(min_overlap={self.min_overlap}, max_diff={self.max_diff}, max_err_milli={self.max_err_milli})"
+
+
+class PairOverlapResult:
+    """The result of a pair overlap (include/ppgpu.h "pair overlap"): the totals `pairs`, `unmapped`, `too_long`,
+    `analysed`, `found`, `negative`, `adapter`, `overlap_bases`, `mismatches`; `clipped` (bases cut from R1, R2);
+    `insert_hist` (numpy int64[2048]: found pairs by insert size) and `median_insert` (the lower median of the
+    found pairs' insert sizes, None when none was found); and the device tensors of the call: `rows` (int32
+    [pairs, 4]: d, overlap, mismatches, insert size; zeros when not found), `found_mask` (uint32 hit-mask words
+    by pair), `windows1` / `windows2` (int32 / uint32 [records, 2] (start, len) rows by record of their set),
+    each None when not asked for."""
+
+    TOTALS = ("pairs", "unmapped", "too_long", "analysed", "found", "negative", "adapter", "overlap_bases", "mismatches")
+
+    def __init__(self, result, insert_hist, rows=None, found_mask=None, windows1=None, windows2=None):
+        for name in self.TOTALS:
+            setattr(self, name, int(getattr(result, name)))
+        self.clipped = tuple(int(x) for x in result.clipped)
+        self.insert_hist = np.asarray(insert_hist, np.int64)
+        self.rows, self.found_mask, self.windows1, self.windows2 = rows, found_mask, windows1, windows2
+
+    @property
+    def median_insert(self):
+        n = int(self.insert_hist.sum())
+        if n == 0:
+            return None
+        return int(np.searchsorted(np.cumsum(self.insert_hist), (n + 1) // 2))
+
+    def __repr__(self):
+        return (f"PairOverlapResult(pairs={self.pairs}, analysed={self.analysed}, found={self.found}, "
+                f"adapter={self.adapter}, clipped={self.clipped}, median_insert={self.median_insert})")
+
+
+def _int_tensor_arg(t, dtypes, what, name):
+    if not (hasattr(t, "data_ptr") and t.is_cuda and t.dtype in dtypes and t.is_contiguous()):
+        raise ValueError(f"{what}: {name} must be a contiguous CUDA tensor of {' / '.join(str(d) for d in dtypes)}")
+    return t
+
+
+def pair_overlap(packed1, packed2, overlap, rec1=None, rec2=None, windows1=None, windows2=None, rows=True,
+                 found_mask=True, device=None):
+    """The pair overlap `overlap` (a PairOverlap) of two packed read sets on one GPU (ppg_pairs_overlap), as a
+    PairOverlapResult.  packed1 / packed2: PackedReads of CUDA tensors (qualities not needed).  rec1 / rec2: int64
+    CUDA tensors, pair i = record rec1[i] of set 1 and rec2[i] of set 2 (None: record i; an entry outside the set
+    leaves the pair out).  windows1 / windows2: int32 / uint32 CUDA tensors of (start, len) rows by record of that
+    set (a trim's), clipped in place to the insert size for found pairs; True starts from whole reads, None: no
+    windows.  rows / found_mask: True allocates, a tensor is written, False / None leaves the output out.
+    Ordered after torch's stream, complete on return."""
+    import torch
+    what = "pair_overlap"
+    for p in (packed1, packed2):
+        if not isinstance(p, PackedReads) or not p.on_device:
+            raise ValueError(f"{what}: expected two PackedReads of CUDA tensors")
+        p._check_device(what)
+    tdev = packed1.seq_off.device
+    if packed2.seq_off.device != tdev:
+        raise ValueError(f"{what}: both read sets must be on one device")
+    dev = device or Device.default(tdev.index if tdev.index is not None else torch.cuda.current_device())
+    o = overlap.struct() if isinstance(overlap, PairOverlap) else PairOverlap().struct() if overlap is None else overlap
+    if not isinstance(o, _lib.PpgPairOverlap):
+        raise ValueError(f"{what}: expected a PairOverlap")
+    sets = (packed1, packed2)
+    maps = [None if r is None else _int_tensor_arg(r, (torch.int64,), what, "rec1 / rec2") for r in (rec1, rec2)]
+    if maps[0] is not None and maps[1] is not None and maps[0].numel() != maps[1].numel():
+        raise ValueError(f"{what}: rec1 and rec2 differ in length")
+    given = [m.numel() for m in maps if m is not None]
+    npairs = given[0] if given else min(packed1.records, packed2.records)
+    if rows is True:
+        rows = torch.zeros((npairs, 4), dtype=torch.int32, device=tdev)
+    elif rows is False:
+        rows = None
+    if rows is not None:
+        _int_tensor_arg(rows, (torch.int32,), what, "rows")
+    if found_mask is True:
+        found_mask = torch.zeros((npairs + 31) // 32, dtype=torch.int32, device=tdev)
+    elif found_mask is False:
+        found_mask = None
+    if found_mask is not None:
+        _int_tensor_arg(found_mask, (torch.int32, torch.uint32), what, "found_mask")
+    wins = []
+    for p, w in zip(sets, (windows1, windows2)):
+        if w is True:
+            w = torch.stack([torch.zeros_like(p.seq_len[:p.records]), p.seq_len[:p.records]], dim=1).contiguous()
+        if w is not None:
+            _int_tensor_arg(w, (torch.int32, torch.uint32), what, "windows")
+        wins.append(w)
+    views = [_lib.PpgPackedView(p.seq_off.data_ptr(), p.seq_len.data_ptr(), p.bases.data_ptr(), p.mask.data_ptr(),
+                                p.qual.data_ptr() if p.qual is not None else None, p.records) for p in sets]
+    ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None and t.numel() else None   # noqa: E731
+    res, hist = _lib.PpgPairOverlapResult(), np.zeros(_lib.PPG_OVERLAP_HIST, np.int64)
+    dev.after_torch()
+    check(lib.ppg_pairs_overlap(dev.handle, C.byref(o), C.byref(views[0]), C.byref(views[1]), ptr(maps[0]), ptr(maps[1]),
+                                npairs, ptr(rows), rows.numel() // 4 if rows is not None else 0, ptr(found_mask),
+                                32 * found_mask.numel() if found_mask is not None else 0,
+                                ptr(wins[0]), wins[0].numel() // 2 if wins[0] is not None else 0,
+                                ptr(wins[1]), wins[1].numel() // 2 if wins[1] is not None else 0,
+                                C.byref(res), _ptr(hist), hist.size), what)
+    return PairOverlapResult(res, hist, rows, None if found_mask is None else found_mask.view(torch.uint32), wins[0], wins[1])
+
+
 class SelectedRecords:
     """The records a mask selects (include/ppgpu.h "record selection"): `bytes` (uint8, the selected
     records' text back to back), `sel_off` (int64, records + 1 offsets into it), `desc` (records x 4:

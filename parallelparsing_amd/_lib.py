@@ -177,6 +177,8 @@ _SIGS = {
     "ppg_pairs_chunk": (C.c_int, [vp, i64, i32, P(vp), P(i64), P(vp), P(i64)]),
     "ppg_pairs_copy_chunk": (C.c_int, [vp, i64, i32, vp, i64, P(i64), vp, i64, P(i64)]),
     "ppg_pairs_emit_stats": (C.c_int, [vp, P(C.c_double), i32]),
+    "ppg_pair_overlap_check": (C.c_int, [vp]),
+    "ppg_pairs_overlap": (C.c_int, [vp, vp, vp, vp, vp, vp, i64, vp, i64, vp, i64, vp, i64, vp, i64, vp, vp, i64]),
 }
 
 
@@ -259,6 +261,28 @@ class PpgReadDedupResult(C.Structure):
 
 
 PPG_DEDUP_USE_WINDOWS, PPG_DEDUP_AND_MASK = 2, 0x100
+
+
+class PpgPackedView(C.Structure):
+    """ppg_packed_view (include/ppgpu.h): device pointers of a packed read set."""
+    _fields_ = [("seq_off", C.c_void_p), ("seq_len", C.c_void_p), ("bases", C.c_void_p), ("mask", C.c_void_p),
+                ("qual", C.c_void_p), ("records", C.c_int64)]
+
+
+class PpgPairOverlap(C.Structure):
+    """ppg_pair_overlap (include/ppgpu.h)."""
+    _fields_ = [("flags", C.c_int64), ("min_overlap", C.c_int64), ("max_diff", C.c_int64), ("max_err_milli", C.c_int64),
+                ("reserved", C.c_int64 * 4)]
+
+
+class PpgPairOverlapResult(C.Structure):
+    """ppg_pair_overlap_result (include/ppgpu.h)."""
+    _fields_ = [("pairs", C.c_int64), ("unmapped", C.c_int64), ("too_long", C.c_int64), ("analysed", C.c_int64),
+                ("found", C.c_int64), ("negative", C.c_int64), ("adapter", C.c_int64), ("overlap_bases", C.c_int64),
+                ("mismatches", C.c_int64), ("clipped", C.c_int64 * 2), ("reserved", C.c_int64 * 5)]
+
+
+PPG_OVERLAP_MAX_LEN, PPG_OVERLAP_HIST = 1024, 2048
 
 
 for _name, (_res, _args) in _SIGS.items():

@@ -149,6 +149,23 @@ struct PpgReadDedup {
 // unique, bases, bases_unique, overflow, max_count, max_first, level_distinct[16], level_reads[16])
 constexpr int kDdAcc = 40;
 
+// a ppg_packed_view and a ppg_pair_overlap (include/ppgpu.h "pair overlap") as the overlap kernel's arguments
+struct PpgPackedView {
+    const int64_t *seq_off;
+    const uint32_t *seq_len;
+    const uint32_t *bases;
+    const uint32_t *mask;
+    const uint8_t *qual;
+    int64_t records;
+};
+struct PpgPairOverlap {
+    int64_t flags, min_overlap, max_diff, max_err_milli, reserved[4];
+};
+// the pair overlap's accumulators: the int64 fields of a ppg_pair_overlap_result in order (pairs, unmapped,
+// too_long, analysed, found, negative, adapter, overlap_bases, mismatches, clipped[2], reserved[5]), then the
+// insert-size histogram of kPoHist bins.  kPoMaxLen: the longest read a pair is analysed with.
+constexpr int kPoAcc = 16, kPoHist = 2048, kPoMaxLen = 1024;
+
 // ppg_sel_copy: the destination bytes one workgroup writes (256 threads x 4 words of 16 B); ppg_sel_place
 // records, per multiple of it inside a batch's destination range, the selected record that holds that byte
 constexpr uint32_t kSelSpan = 16384;

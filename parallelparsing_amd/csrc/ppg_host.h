@@ -114,6 +114,7 @@ struct ppg_ctx {
     double ix_stats[kIxStats] = {0};   // timings / counts of the last GPU CreateIndex (ppg_index_build_gpu_stats)
     uint8_t *stage = nullptr;           // pinned device -> host staging (CreateIndex windows), kept across calls
     size_t stage_n = 0;
+    int overlap_grid = 0;               // ppg_po_overlap's grid (0: the default; the tests force small ones)
 };
 
 template <class T>

@@ -135,6 +135,14 @@ PPG_WEAK hipError_t ppg_launch_dd_decide(hipStream_t s, const PpgBatchView &v, c
 PPG_WEAK hipError_t ppg_launch_dd_levels(hipStream_t s, const uint64_t *table, uint64_t slots, uint64_t *acc);
 PPG_WEAK hipError_t ppg_launch_dd_totals(hipStream_t s, const uint64_t *acc, int64_t *host_result);
 
+// ---- ppg_pairoverlap.hip ----
+// Weak for the same reason (pairoverlap_linked, ppg_stages.cpp).  Two packed read sets, not a batch: rows of
+// four int32, found in the hit-mask format, win1 / win2 rows of two uint32, acc kPoAcc + kPoHist values.
+PPG_WEAK hipError_t ppg_launch_pair_overlap(hipStream_t s, const PpgPackedView &s1, const PpgPackedView &s2,
+                                            const int64_t *rec1, const int64_t *rec2, int64_t npairs,
+                                            const PpgPairOverlap *po, int32_t *rows, uint32_t *found, uint32_t *win1,
+                                            uint32_t *win2, uint64_t *acc, int blocks, int cus);
+
 // ---- ppg_seqselect.hip ----
 // Weak for the same reason (select_linked, ppg_stages.cpp).
 PPG_WEAK hipError_t ppg_launch_sel_count(hipStream_t s, const PpgBatchView &v, const uint32_t *mask, uint64_t bit0,

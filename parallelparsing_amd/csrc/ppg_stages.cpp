@@ -3,7 +3,8 @@
 // (ppg_readfilter.hip), read trim (ppg_readtrim.hip), read dedup (ppg_readdedup.hip), read profile
 // (ppg_readprofile.hip) and record selection (ppg_seqselect.hip): for each its
 // pieces on one batch, its C entry points (one-shot on a one-batch shard, the hook of every batch of a
-// run, and what the last run left) and the measurement hook of its tools/*_probe.py.
+// run, and what the last run left) and the measurement hook of its tools/*_probe.py.  The pair overlap
+// (ppg_pairoverlap.hip) is here as well: it has no batch, it reads two packed read sets the pack stage wrote.
 //
 // A batch's hooks run from one place, shard_batch_hooks, called once by batch_collect (ppg_api.cpp).  The
 // unit kernels of query, filter, trim, dedup and profile read one layout of the batch (StageLayout, ppg_host.h), which
@@ -23,7 +24,10 @@
 static_assert(sizeof(ppg_seq_query_result) == 8 * 8 && sizeof(ppg_read_filter_result) == 8 * kRfAcc &&
                   sizeof(ppg_read_trim_result) == 8 * kRtAcc && sizeof(ppg_read_profile_result) == 8 * kRpFixed &&
                   sizeof(ppg_read_profile) == sizeof(PpgReadProfile) && PPG_PROFILE_MAX_POS == kRpMaxPos &&
-                  sizeof(ppg_read_dedup_result) == 8 * kDdAcc && sizeof(ppg_read_dedup) == sizeof(PpgReadDedup),
+                  sizeof(ppg_read_dedup_result) == 8 * kDdAcc && sizeof(ppg_read_dedup) == sizeof(PpgReadDedup) &&
+                  sizeof(ppg_pair_overlap_result) == 8 * kPoAcc && sizeof(ppg_pair_overlap) == sizeof(PpgPairOverlap) &&
+                  sizeof(ppg_packed_view) == sizeof(PpgPackedView) && PPG_OVERLAP_MAX_LEN == kPoMaxLen &&
+                  PPG_OVERLAP_HIST == kPoHist,
               "a stage's result struct is its accumulators");
 
 static bool seq_linked() {   // (weak references, ppg_launch.h: absent from the host-only sanitizer build)
@@ -387,6 +391,54 @@ int shard_read_dedup(ppg_shard *sh, int32_t b0, int32_t b1, const uint32_t *recs
 static void readdedup_outputs(const DedupStage &d, int32_t n, int64_t *chunk_unique, void *result) {
     d.outputs(n, chunk_unique, result, sizeof(ppg_read_dedup_result));
     if (!d.host.p && result) ((ppg_read_dedup_result *)result)->max_first = -1;   // no batch ran: an empty table
+}
+
+// ---- pair overlap (ppg_pairoverlap.hip) ----
+// Not a batch's stage: it works on two packed read sets in caller memory, on the ctx stream.
+static bool pairoverlap_linked() { return ppg_launch_pair_overlap != nullptr; }
+
+// the rules of include/ppgpu.h "pair overlap"; host only
+static bool pairoverlap_ok(const void *overlap, PpgPairOverlap *out) {
+    if (!overlap) return false;
+    PpgPairOverlap o;
+    memcpy(&o, overlap, sizeof o);
+    if (o.flags != 0 || o.min_overlap < 1 || o.max_diff < 0 || o.max_err_milli < 0 || o.max_err_milli > 1000) return false;
+    for (int64_t r : o.reserved)
+        if (r != 0) return false;
+    if (out) *out = o;
+    return true;
+}
+
+// a ppg_packed_view with every plane but qual, aligned as the packed reads are written
+static bool packed_view_ok(const void *set, PpgPackedView *out) {
+    if (!set) return false;
+    memcpy(out, set, sizeof *out);
+    return out->seq_off && out->seq_len && out->bases && out->mask && out->records >= 0 &&
+           ((uintptr_t)out->seq_off & 7) == 0 && ((uintptr_t)out->seq_len & 3) == 0 && ((uintptr_t)out->bases & 7) == 0 &&
+           ((uintptr_t)out->mask & 3) == 0;
+}
+
+struct PairOverlapArgs {
+    PpgPairOverlap po;
+    PpgPackedView s1, s2;
+};
+
+// PPG_ARG_ERROR / PPG_BUF_ERROR of ppg_pairs_overlap, before anything is written
+static int pairoverlap_args(ppg_ctx *ctx, const void *overlap, const void *set1, const void *set2, const int64_t *rec1,
+                            const int64_t *rec2, int64_t npairs, const void *rows, int64_t row_cap, const uint32_t *found,
+                            int64_t mask_cap, const void *win1, int64_t win_cap1, const void *win2, int64_t win_cap2,
+                            const int64_t *hist, int64_t hist_cap, PairOverlapArgs &a) {
+    if (!ctx || !pairoverlap_ok(overlap, &a.po) || !packed_view_ok(set1, &a.s1) || !packed_view_ok(set2, &a.s2)) return PPG_ARG_ERROR;
+    if (npairs < 0 || row_cap < 0 || mask_cap < 0 || mask_cap % 32 != 0 || win_cap1 < 0 || win_cap2 < 0 || hist_cap < 0)
+        return PPG_ARG_ERROR;
+    if (((uintptr_t)rec1 & 7) || ((uintptr_t)rec2 & 7) || ((uintptr_t)rows & 15) || ((uintptr_t)found & 3) ||
+        ((uintptr_t)win1 & 7) || ((uintptr_t)win2 & 7))
+        return PPG_ARG_ERROR;
+    if ((!rec1 && npairs > a.s1.records) || (!rec2 && npairs > a.s2.records)) return PPG_ARG_ERROR;   // the identity map
+    if ((rows && npairs > row_cap) || (found && npairs > mask_cap) || (win1 && a.s1.records > win_cap1) ||
+        (win2 && a.s2.records > win_cap2) || (hist && hist_cap < kPoHist))
+        return PPG_BUF_ERROR;
+    return PPG_OK;
 }
 
 // ---- record selection (ppg_seqselect.hip) ----
@@ -886,6 +938,35 @@ int ppg_shard_readdedup_ready(ppg_shard *sh, int64_t *chunk_unique, void *result
     return 1;
 }
 
+// ---- pair overlap: one blocking call on the ctx stream ----
+int ppg_pair_overlap_check(const void *overlap) { return pairoverlap_ok(overlap, nullptr) ? PPG_OK : PPG_ARG_ERROR; }
+
+int ppg_pairs_overlap(ppg_ctx *ctx, const void *overlap, const void *set1, const void *set2, const int64_t *dev_rec1,
+                      const int64_t *dev_rec2, int64_t npairs, void *dev_rows, int64_t row_cap, uint32_t *dev_found_mask,
+                      int64_t mask_cap, void *dev_windows1, int64_t win_cap1, void *dev_windows2, int64_t win_cap2,
+                      void *result, int64_t *hist, int64_t hist_cap) {
+    PairOverlapArgs a;
+    if (int rc = pairoverlap_args(ctx, overlap, set1, set2, dev_rec1, dev_rec2, npairs, dev_rows, row_cap, dev_found_mask,
+                                  mask_cap, dev_windows1, win_cap1, dev_windows2, win_cap2, hist, hist_cap, a))
+        return rc;
+    if (!pairoverlap_linked()) return PPG_UNSUPPORTED;
+    HIPCHK(hipSetDevice(ctx->device));
+    hipStream_t s = ctx->stream;
+    int cus = 0;
+    HIPCHK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, ctx->device));
+    DevBuf<uint64_t> acc;
+    HIPCHK(acc.alloc(kPoAcc + kPoHist));
+    HIPCHK(hipMemsetAsync(acc.p, 0, 8 * (size_t)(kPoAcc + kPoHist), s));
+    HIPCHK(ppg_launch_pair_overlap(s, a.s1, a.s2, dev_rec1, dev_rec2, npairs, &a.po, (int32_t *)dev_rows, dev_found_mask,
+                                   (uint32_t *)dev_windows1, (uint32_t *)dev_windows2, acc.p, ctx->overlap_grid, cus));
+    std::vector<int64_t> h((size_t)(kPoAcc + kPoHist));
+    HIPCHK(hipMemcpyAsync(h.data(), acc.p, 8 * h.size(), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    if (result) memcpy(result, h.data(), sizeof(ppg_pair_overlap_result));
+    if (hist) memcpy(hist, h.data() + kPoAcc, 8 * (size_t)kPoHist);
+    return PPG_OK;
+}
+
 // ---- record selection: the sequence queries entry points' counterparts ----
 static bool select_bufs_ok(const int64_t *recno, const int64_t *sel_off, const uint32_t *desc, int64_t sel_cap,
                            const uint8_t *bytes, int64_t byte_cap) {
@@ -1266,6 +1347,43 @@ int ppgx_readdedup_times(ppg_shard *sh, const void *dedup, const void *dev_windo
 int ppgx_readprofile_grid(ppg_shard *sh, int blocks) {
     if (!sh || blocks < 0) return PPG_ARG_ERROR;
     sh->profile.grid = blocks;
+    return PPG_OK;
+}
+
+// tools/pairoverlap_probe.py.  ms[0]: the overlap kernel over pairs (i, i) of the two sets, with the zeroing of
+// its accumulators, writing rows and found bits to scratch of the hook's own; no windows.  The stream is the
+// ctx's.
+int ppgx_pairoverlap_times(ppg_ctx *ctx, const void *overlap, const void *set1, const void *set2, int64_t npairs, int reps,
+                           float *ms) {
+    PairOverlapArgs a;
+    if (!ms || reps < 1) return PPG_ARG_ERROR;
+    if (int rc = pairoverlap_args(ctx, overlap, set1, set2, nullptr, nullptr, npairs, nullptr, 0, nullptr, 0, nullptr, 0,
+                                  nullptr, 0, nullptr, 0, a))
+        return rc;
+    if (!pairoverlap_linked()) return PPG_UNSUPPORTED;
+    HIPCHK(hipSetDevice(ctx->device));
+    hipStream_t s = ctx->stream;
+    int cus = 0;
+    HIPCHK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, ctx->device));
+    DevBuf<uint64_t> acc;
+    DevBuf<int32_t> rows;
+    DevBuf<uint32_t> found;
+    HIPCHK(acc.alloc(kPoAcc + kPoHist));
+    HIPCHK(rows.alloc(4 * (size_t)npairs));
+    HIPCHK(found.alloc((size_t)npairs / 32 + 1));
+    return time_steps(s, 1, reps, ms, [&](int) {
+        const hipError_t e = hipMemsetAsync(acc.p, 0, 8 * (size_t)(kPoAcc + kPoHist), s);
+        return e != hipSuccess ? e
+                               : ppg_launch_pair_overlap(s, a.s1, a.s2, nullptr, nullptr, npairs, &a.po, rows.p, found.p, nullptr,
+                                                         nullptr, acc.p, ctx->overlap_grid, cus);
+    });
+}
+
+// ppg_po_overlap's grid on this ctx from now on (0: the default).  The tests force one block and uneven shares
+// with it.
+int ppgx_pairoverlap_grid(ppg_ctx *ctx, int blocks) {
+    if (!ctx || blocks < 0) return PPG_ARG_ERROR;
+    ctx->overlap_grid = blocks;
     return PPG_OK;
 }
 

@@ -17,7 +17,7 @@ import ctypes as C
 
 import numpy as np
 
-from . import Device, IndexIO, Shard, records_from_descriptors
+from . import Device, IndexIO, PackedReads, PairOverlap, Shard, pair_overlap, records_from_descriptors
 from ._lib import lib, check, PpgPairResult
 
 DUP = -2      # key of a record parsed twice (Q1), dropped before pairing
@@ -202,6 +202,37 @@ class PairedFASTQ:
     @property
     def chunks(self):
         return (self.pairs + self.K - 1) // self.K
+
+    def _packed(self, f):
+        """File f's reads packed without qualities, as a PackedReads on the device: one call on a one-batch
+        shard, the pack hook and a re-run on a multi-batch one (whose output does not stay resident)."""
+        sh = self.shards[f]
+        if sh.batches == 1:
+            return sh.pack_sequences(quality=False)
+        tot, rec = sh.seq_bases()
+        packed = PackedReads.empty(rec, tot, False, self.dev.device)
+        sh.set_seqpack(packed).run()
+        ok = sh.seqpack_ready
+        sh.set_seqpack(None)
+        self._it, self._win = None, (0, 0)   # the re-run ends an emission in progress
+        if not ok:
+            raise ValueError("PairedFASTQ.Overlap: the shard's run did not fill the packed reads")
+        return packed
+
+    def Overlap(self, overlap=None, windows=False):
+        """The pair overlap (include/ppgpu.h "pair overlap") of every pair, as a PairOverlapResult: insert
+        sizes, the insert-size histogram and, with windows=True, whole-read (start, len) rows of both files
+        clipped to the insert size (`windows1` / `windows2`, by shard record number: what
+        Shard.profile_reads(windows=...) and dedup_reads take).  Both files are packed on the device; the maps
+        are the pairing's (Pairs.records), so a record parsed twice is left out exactly as the pairing leaves
+        it out, and its windows row stays the whole read.  overlap: a PairOverlap (None: fastp's defaults)."""
+        import torch
+        packed = [self._packed(f) for f in (0, 1)]
+        tdev = torch.device("cuda", self.dev.device)
+        maps = [torch.from_numpy(np.ascontiguousarray(self._pairs.records(f, 0, self.pairs))).to(tdev) for f in (0, 1)]
+        w = True if windows else None
+        return pair_overlap(packed[0], packed[1], overlap if overlap is not None else PairOverlap(), maps[0], maps[1],
+                            windows1=w, windows2=w, device=self.dev)
 
     def pair_chunks(self):
         """Yield (j, R1 records, R2 records) for every pair chunk in order."""
