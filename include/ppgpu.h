@@ -187,7 +187,16 @@ int ppg_decompress_chunk_split_stats(ppg_ctx *ctx, int64_t *chunks, int64_t *sid
  * (comp_len = Index[first+n].Input - Index[first].Input + 1).  comp_on_device != 0 means comp
  * is already a device pointer on this GPU (4-byte aligned, readable 64 bytes past comp_len);
  * otherwise it is copied.  out_capacity bounds the device output buffer: chunks are decoded
- * in batches whose outputs fit, the buffer being reused (0 = whole shard at once). */
+ * in batches whose outputs fit, the buffer being reused (0 = whole shard at once).
+ * A range that ends early is taken when it ends inside the last chunk's own bytes (at least 8 bytes
+ * past Index[first+n-1].Input-1: a file that ends early): that chunk needs bits past the slice it was
+ * handed and fails with PPG_DATA_ERROR (Core.cs:174), every other chunk is unaffected.  Any other
+ * comp_len is PPG_ARG_ERROR.
+ * A failed chunk (status != 0) has no records: it takes no record numbers, no units and no rows, the
+ * chunks after it are numbered as if it were empty, and every record stage below counts 0 for it.
+ * ppg_shard_run goes through every batch and every hook before it returns the first failed chunk's
+ * status, so nothing a hook wrote counts as ready; the one-shot stage calls on a one-batch shard
+ * work after such a run and see the good chunks' records alone. */
 typedef struct ppg_shard ppg_shard;
 
 int ppg_shard_create(ppg_ctx *ctx, const ppg_index *ix, int32_t first, int32_t n, const void *comp, int64_t comp_len,
@@ -933,6 +942,13 @@ void ppg_pairs_free(ppg_pairs *p);
  *      and a pair chunk that straddles a batch boundary is carried across; nothing else may run the
  *      shards until the emission is done.  N ranks: rank r owns the pair chunks that start in its
  *      R1 range; the shards must be one-batch (resident; else PPG_UNSUPPORTED).
+ *      The batches run again run none of the shard's hooks: neither ppg_shard_set_keys nor a record
+ *      stage (ppg_shard_set_seqpack, _seqquery, _readfilter, _readtrim, _readdedup, _readprofile,
+ *      _select).  From the check on -- after every window, after an emission that is stopped early,
+ *      after the last window and through any further emission on the same check -- every attached
+ *      stage's *_ready answer, its result struct, its per-chunk counts and every caller buffer it
+ *      wrote (mask, windows rows, metrics, first rows, table, packed planes, selected records) are
+ *      bit for bit what the shard's own ppg_shard_run left.
  *  ppg_pairs_emit_run    one rank, no check first: the emission drives the shards' own run.  Both
  *      shards carry a keys buffer (ppg_shard_set_keys); their batches run once each, in order, as
  *      the windows advance -- each batch's records numbered (its Q1 duplicates found from its keys)
@@ -940,6 +956,12 @@ void ppg_pairs_free(ppg_pairs *p);
  *      the last window (PPG_STREAM_END) both shards stand as ppg_shard_run leaves them and
  *      ppg_pairs_check follows (it may report mismatches the windows already emitted).  A caller
  *      that stops early leaves the shards unrun.
+ *      The emission is the shards' run for their record stages too: every attached stage runs once
+ *      per batch, in hook order.  From the call until the last window every stage is unready (its
+ *      *_ready answer is 0), one that an earlier ppg_shard_run left ready included; after
+ *      PPG_STREAM_END every attached stage is ready, with the results and buffers ppg_shard_run
+ *      leaves on the same shard.  A caller that stops early, or a run that fails, leaves every stage
+ *      unready.
  *  ppg_pairs_emit_next   packs the next window of this rank's pair chunks [*j0, *j1) on the device;
  *      PPG_STREAM_END when there is none.  N ranks: the first call is collective (every rank calls
  *      it: the records a rank does not hold move from their ranks over ppg_comm_alltoallv -- RCCL

@@ -406,7 +406,12 @@ int shard_prepare(ppg_shard *sh, const ppg_index *ix, int32_t first, int32_t n, 
     const int64_t base_byte = P[(size_t)first].input - 1;
     if (base_byte < 0) return PPG_ARG_ERROR;
     if (const int v = ppg_index_validate(ix, first, n); v != PPG_OK) return v;
-    if (comp_len != P[(size_t)first + n].input - P[(size_t)first].input + 1) return PPG_ARG_ERROR;
+    // The whole range, or one that ends early inside the last chunk's own bytes (a file that ends early,
+    // LazyFileReader.cs:63-69: zlib is handed the short slice, and that chunk alone fails, Core.cs:174):
+    // every chunk's first word is inside comp, and shard_prepare_specs bounds the bits at comp's end.
+    const int64_t whole = P[(size_t)first + n].input - P[(size_t)first].input + 1;
+    const int64_t least = n > 0 ? P[(size_t)first + n - 1].input - P[(size_t)first].input + 8 : whole;
+    if (comp_len > whole || comp_len < std::min(least, whole)) return PPG_ARG_ERROR;
     if (ix->windows.size() < ((size_t)first + n) * kWin) return PPG_ARG_ERROR;
     std::vector<ChunkSpec> spec((size_t)n);
     for (int32_t i = 0; i < n; i++)
@@ -468,7 +473,8 @@ int shard_prepare_specs(ppg_shard *sh, const ChunkSpec *spec, int32_t n, const u
             PpgInflateJob &J = sh->h_jobs[(size_t)i];
             const int64_t cb = spec[i].comp_byte;   // comp offset of file byte from.Input - 1
             J.bit_start = (uint64_t)(8 * (cb + 1) - from.bits);
-            J.bit_limit = (uint64_t)(8 * (cb + 1 + to.input - from.input));
+            // (comp's end bounds it too: the same value for a whole range, less for shard_prepare's short one)
+            J.bit_limit = std::max<uint64_t>(J.bit_start, (uint64_t)std::min<int64_t>(8 * (cb + 1 + to.input - from.input), 8 * comp_len));
             J.out_off = (uint64_t)(pos - bbase);
             J.out_len = (uint64_t)ulen;
             J.dict_off = (uint64_t)i * kWin;

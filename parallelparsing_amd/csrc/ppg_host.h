@@ -318,6 +318,9 @@ struct ppg_shard {
     int64_t *keys_dev = nullptr;
     int64_t keys_cap = 0;
     int keys_written = 0;   // the last successful run filled keys_dev (stages_run_end)
+    // a batch run again for the pair emission (ppg_pairs.hip: rerun_launch / rerun_collect): its hooks are
+    // suspended, keys and record stages alike, so what the shard's own run left stays as it is
+    int hooks_off = 0;
     // the record stages (ppg_stages.cpp), run by shard_batch_hooks on every batch while its output is resident
     StageLayout lay;
     PackStage pack;
@@ -375,8 +378,10 @@ bool pread_parallel(int fd, uint8_t *dst, int64_t off, int64_t len, int threads)
 // shard's stream; the calls said to block synchronise it. ----
 PpgBatchView batch_view(const ppg_shard *sh, int32_t b0, int32_t b1, const uint32_t *recs);
 // batch_collect's one call: the batch's hooks in the order keys, pack, query, filter, trim, dedup, profile, select
+// (none of them while sh->hooks_off)
 int shard_batch_hooks(ppg_shard *sh, int32_t b0, int32_t b1, int64_t tot);
-// ppg_shard_run's two: no hook's output counts as written during a run; a run that succeeded wrote them all
+// ppg_shard_run's two, and the fused pair emission's (ppg_pairs_emit_run: begin at the call, end after the last
+// window): no hook's output counts as written during a run; a run that succeeded wrote them all
 void stages_run_begin(ppg_shard *sh);
 void stages_run_end(ppg_shard *sh, bool ok);
 // packed reads.  layout: per-chunk padded bases, their scan and the batch's total (blocks); pack: seq_off /

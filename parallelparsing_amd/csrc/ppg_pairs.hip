@@ -156,7 +156,6 @@ extern "C" __global__ __launch_bounds__(256) void ppg_pack_segs(const PpgPackSeg
 struct RerunSave {
     int64_t tot = 0;
     float ti = 0, tp = 0, tt = 0;
-    int64_t *keys = nullptr;
 };
 
 // ppg_pairs_emit_*: the record-aligned pair chunks (see the ABI comment in include/ppgpu.h)
@@ -543,16 +542,17 @@ int seg_pack(PairEmit &E, const std::vector<PpgPackSeg> &seg, uint8_t *dst, uint
 
 // batch b of a shard's batches run again, its output resident (one rank: the windows advance over
 // the batches): launch, then collect (two shards' batches are in flight together); the shard's
-// record totals, bases, keys and timing are left as its run left them
+// record totals, bases and timing are left as its run left them, and its hooks -- the keys and every
+// record stage -- are suspended (hooks_off), so their results and the caller's buffers are too
 int rerun_launch(ppg_shard *sh, int32_t b, RerunSave &sv) {
     const auto [b0, b1] = sh->batches[(size_t)b];
-    sv = RerunSave{sh->total_records, sh->t_inflate, sh->t_parse, sh->t_total, sh->keys_dev};
+    sv = RerunSave{sh->total_records, sh->t_inflate, sh->t_parse, sh->t_total};
     sh->total_records = sh->h_base[(size_t)b0];   // descriptors rewritten where the run wrote them
-    sh->keys_dev = nullptr;
+    sh->hooks_off = 1;
     const int rc = batch_launch(sh, b0, b1);
     if (rc != PPG_OK) {
         sh->total_records = sv.tot;
-        sh->keys_dev = sv.keys;
+        sh->hooks_off = 0;
     }
     return rc;
 }
@@ -565,7 +565,7 @@ int rerun_collect(ppg_shard *sh, int32_t b, const RerunSave &sv) {
     sh->t_inflate = sv.ti;
     sh->t_parse = sv.tp;
     sh->t_total = sv.tt;
-    sh->keys_dev = sv.keys;
+    sh->hooks_off = 0;
     return rc;
 }
 
@@ -749,7 +749,8 @@ int emit_next_local(ppg_pairs *p, int64_t *j0, int64_t *j1) {
 // Batch b of file f has just run for the first time: its chunks' parse info, the duplicates among
 // its records (ppg_key_dups over its keys; SURVEY Q1: at most one per chunk, so the numbering map
 // grows batch by batch), its deduplicated record range; after the file's last batch the shard is
-// finished exactly as ppg_shard_run leaves it (results, status, keys marked written).
+// finished exactly as ppg_shard_run leaves it (results, status, keys marked written).  Its record
+// stages stay unready until the last window is out (emit_next_fused: stages_run_end).
 int fused_collected(ppg_pairs *p, int f, int32_t b) {
     PairEmit &E = p->em;
     ppg_shard *sh = E.sh[f];
@@ -846,6 +847,8 @@ int emit_next_fused(ppg_pairs *p, int64_t *j0, int64_t *j1) {
                 }
             E.npc = (std::min(p->local[0], p->local[1]) + K - 1) / K;
             E.j_hi = E.npc;
+            // both runs are complete (a failing batch has returned above): what their hooks wrote counts
+            for (int f = 0; f < 2; f++) stages_run_end(E.sh[f], true);
             return PPG_STREAM_END;
         }
         // 1. each file's resident batch must complete pair chunk e (the first part carried over when
@@ -1243,7 +1246,7 @@ int ppg_pairs_emit_run(ppg_pairs *p, ppg_shard *r1, ppg_shard *r2, int64_t pair_
     for (int f = 0; f < 2; f++) {
         ppg_shard *sh = E.sh[f];
         shard_reset(sh);
-        sh->keys_written = 0;
+        stages_run_begin(sh);   // nothing is ready until the last window (a caller that stops early: never)
         sh->last_rc = PPG_OK;
         E.clen[f] = E.cnrec[f] = 0;
         E.done[f] = false;

@@ -509,6 +509,7 @@ static int select_hook(ppg_shard *sh, int32_t b0, int32_t b1, const uint32_t *re
 // profile reads the mask and the rows as they were left, and the selection, last, hands over the product.  A
 // cap that the batch would exceed fails with PPG_BUF_ERROR before the stage writes anything.
 int shard_batch_hooks(ppg_shard *sh, int32_t b0, int32_t b1, int64_t tot) {
+    if (sh->hooks_off) return PPG_OK;   // a batch run again for the pair emission: the run's outputs stand
     const int64_t rec0 = sh->total_records, after = rec0 + tot;
     const uint32_t *recs = sh->recs.p + 4 * (uint64_t)rec0;
     // The run's first batch, where the accumulators and the selection's totals restart.  The pack's base

@@ -103,10 +103,10 @@ class Pairs:
         """The same windows with no check first, the emission driving the shards' own run
         (ppg_pairs_emit_run): each output batch of both shards decoded once and its records packed
         while resident.  Both shards need attach_keys; after the last window both have run (as
-        Shard.run leaves them) and check() may follow."""
+        Shard.run leaves them) and check() may follow.  The shards' record stages (set_seqpack ..
+        set_select) run once per batch and are ready after the last window, not before."""
         for r in (r1, r2):
-            if r._on_device:
-                r._torch_order()   # the caller may have rewritten comp since the last run
+            r._torch_order()   # the caller may have rewritten comp (or the hooks' tensors) since the last run
         check(lib.ppg_pairs_emit_run(self._h, r1.handle, r2.handle, int(pair_chunk), int(window_bytes)),
               "ppg_pairs_emit_run")
         j0, j1 = C.c_int64(), C.c_int64()
