@@ -1039,7 +1039,7 @@ typedef struct {
     const uint32_t *seq_len;
     const uint32_t *bases;
     const uint32_t *mask;
-    const uint8_t *qual;     /* may be NULL; not read */
+    const uint8_t *qual;     /* the overlap: may be NULL, not read; the merge: required */
     int64_t records;
 } ppg_packed_view;
 typedef struct {
@@ -1067,6 +1067,101 @@ int ppg_pairs_overlap(ppg_ctx *ctx, const void *overlap, const void *set1, const
                       const int64_t *dev_rec2, int64_t npairs, void *dev_rows, int64_t row_cap,
                       uint32_t *dev_found_mask, int64_t mask_cap, void *dev_windows1, int64_t win_cap1,
                       void *dev_windows2, int64_t win_cap2, void *result, int64_t *hist, int64_t hist_cap);
+
+/* ---- pair merge: one consensus read per overlapping pair, as a third packed read set ----
+ * What fastp --merge / --correction, PEAR and FLASH make of the overlap: the fragment's bases once, every
+ * base that both mates cover decided by the better of the two observations.  The result is a packed read set
+ * ("packed reads" above), so it feeds everything that takes one, a second pair overlap among them; no read
+ * text leaves the device.
+ * Inputs.  Set 1 and set 2 as ppg_packed_view, and the maps dev_rec1 / dev_rec2, exactly as in "pair overlap"
+ * (NULL is the identity and npairs must then not exceed that set's records; an entry outside the set makes the
+ * pair unmapped; no entry makes a kernel read outside the planes).  Both qual planes are required here and
+ * 16-byte aligned (ppg_pairs_merge_size does not read them and takes NULL).  dev_rows: device memory, 16-byte
+ * aligned, row_cap >= npairs rows of four int32 in the overlap's row format (d, ov, mis, I); normally the
+ * overlap wrote them, a caller may zero a row to leave that pair out.  ov and mis are not read, and d and I are
+ * trusted for nothing: a row that does not fit its pair is counted and skipped.
+ * Parameters.  A ppg_pair_merge: eight int64_t, 64 bytes, passed as const void *.  flags 0; qual_hi and
+ * qual_lo are quality bytes as they stand in the file (no offset is subtracted), 0 <= qual_lo < qual_hi <= 255;
+ * reserved 0.  They only decide what is counted as corrected, never a base.  ppg_pair_merge_check is host
+ * only: PPG_ARG_ERROR for a NULL struct or a field outside these ranges, PPG_OK otherwise; both other entry
+ * points that take the struct apply it.  The Python layer's defaults are qual_hi 63 and qual_lo 47 ('?' and
+ * '/': phred 30 and 14 at offset 33); they are defined by these values, not by another tool's behaviour.
+ * Which pairs merge, in signed 64-bit integers.  Pair i has the lengths L1, L2 of the overlap and the row
+ * (d, ., ., I).  It is, the first that applies:
+ *   unmapped   as in the overlap;
+ *   too_long   L1 or L2 above PPG_OVERLAP_MAX_LEN;
+ *   unmerged   I == 0;
+ *   stale      I != 0 but not (-L2 < d < L1 and I == L2 + d);
+ *   merged     otherwise; then 1 <= I <= 2047.
+ * The merged read has M = I bases; position p in [0, I) is a read-1 coordinate.  With c, n the 2-bit code and
+ * the mask bit of the packed format and q the byte of the set's qual plane:
+ *   side 1 covers p iff p < L1 and gives (c1(p), n1(p), q1(p));
+ *   side R covers p iff p >= d and gives, with t = p - d, (3 - c2(L2-1-t), n2(L2-1-t), q2(L2-1-t)).
+ * Every p is covered (a gap would need L1 <= p < d, but d < L1).  A p one side covers takes that side.  A p both
+ * cover takes side R iff (n1 and not nR) or (n1 == nR and qR > q1), else side 1: a base beats an N, then the
+ * higher quality byte wins, a tie goes to read 1 -- whether the two bases agree or not.  The output's mask bit
+ * at p is the taken side's n, its code the taken side's code or 0 if that n is set, its qual byte the taken
+ * side's q.  Bases of either mate outside [0, I) are read-through and are dropped (the overlap's clip).
+ * Output.  The merged pairs in pair order, compacted: merged record m is the m-th merged pair.  Caller device
+ * memory with the pointers, alignments and caps of ppg_shard_pack_seq: dev_seq_off (rec_cap + 1 entries),
+ * dev_seq_len, dev_bases, dev_mask, dev_qual (NULL for no quality plane; the choice uses the input qualities
+ * all the same), base_cap a multiple of 32; and dev_pair_of, optional, int64 [rec_cap], 8-byte aligned: the pair
+ * index of each merged record.  seq_off[0] = 0, seq_off[m+1] = seq_off[m] + 32 * ceil(M_m / 32); positions
+ * M <= i < P are 0 in all planes, every word / byte below seq_off[merged] is written and nothing at or past the
+ * caps; entries of seq_len and pair_of from `merged` on are not written.  The planes are a function of the
+ * inputs alone.
+ * Result.  A host ppg_pair_merge_result, declared below, 16 int64_t.  Over the positions both sides cover
+ * (overlap_bases): disagree counts those with both n clear and different codes, n_filled those with exactly
+ * one n set, n_both those with both; the rest agree (overlap_bases - disagree - n_filled - n_both; not
+ * stored).  Among the disagreements: from2 took side R, ties have qR == q1, corrected[0] took side R with
+ * qR >= qual_hi and q1 <= qual_lo (read 1 overruled), corrected[1] took side 1 with q1 >= qual_hi and
+ * qR <= qual_lo.  With rows exactly as the overlap wrote them, overlap_bases is the overlap's and
+ * disagree + n_filled + n_both its mismatches.
+ *  ppg_pair_merge_check   above.
+ *  ppg_pairs_merge_size   *merged and *padded_bases = seq_off[merged]: the caps a merge needs.
+ *  ppg_pairs_merge        sizes first; PPG_BUF_ERROR, nothing written, when npairs > row_cap, merged > rec_cap
+ *                         or padded_bases > base_cap.  npairs == 0 and "nothing merged" are PPG_OK with
+ *                         seq_off[0] = 0 written.
+ * PPG_ARG_ERROR: a NULL ctx, view, view plane (qual as said), rows (with npairs > 0) or output plane other than
+ * dev_qual and dev_pair_of, a negative count or cap, a misaligned pointer, a base_cap that is no multiple of 32.
+ * An output plane of capacity 0 holds nothing and may be NULL: dev_seq_len with rec_cap 0, dev_bases and dev_mask
+ * with base_cap 0 (dev_seq_off always has its entry 0), so a caller that sized a merge of nothing need not
+ * invent addresses.
+ * The calls run on the ctx stream and block, like the other one-shot calls; the caller orders the producers of
+ * the planes and rows before them with ppg_ctx_wait_stream.  The rows are read twice, once to size and once to
+ * place: the sets, the maps and the rows must not change while a call runs, or the caps that were checked are
+ * not the caps that are used. */
+typedef struct {
+    int64_t flags;           /* 0 */
+    int64_t qual_hi;         /* corrected: the taken side's quality byte is at least this ... */
+    int64_t qual_lo;         /* ... and the other side's at most this */
+    int64_t reserved[5];     /* 0 */
+} ppg_pair_merge;
+typedef struct {
+    int64_t pairs;           /* pairs given */
+    int64_t unmapped;
+    int64_t too_long;
+    int64_t unmerged;        /* I == 0 */
+    int64_t stale;           /* a row that does not fit its pair */
+    int64_t merged;
+    int64_t merged_bases;    /* sum of M */
+    int64_t padded_bases;    /* seq_off[merged] */
+    int64_t overlap_bases;   /* positions both sides cover */
+    int64_t disagree;        /* both bases, different codes */
+    int64_t from2;           /* ... where side R was taken */
+    int64_t ties;            /* ... where qR == q1 */
+    int64_t n_filled;        /* exactly one side N */
+    int64_t n_both;
+    int64_t corrected[2];    /* read 1 overruled, read 2 overruled */
+} ppg_pair_merge_result;
+int ppg_pair_merge_check(const void *merge);
+int ppg_pairs_merge_size(ppg_ctx *ctx, const void *set1, const void *set2, const int64_t *dev_rec1,
+                         const int64_t *dev_rec2, int64_t npairs, const void *dev_rows, int64_t row_cap,
+                         int64_t *merged, int64_t *padded_bases);
+int ppg_pairs_merge(ppg_ctx *ctx, const void *merge, const void *set1, const void *set2, const int64_t *dev_rec1,
+                    const int64_t *dev_rec2, int64_t npairs, const void *dev_rows, int64_t row_cap,
+                    int64_t *dev_seq_off, uint32_t *dev_seq_len, int64_t rec_cap, uint32_t *dev_bases,
+                    uint32_t *dev_mask, uint8_t *dev_qual, int64_t base_cap, int64_t *dev_pair_of, void *result);
 
 /* Library build string (kernel ISA, version). */
 const char *ppg_version(void);

@@ -52,6 +52,30 @@ public sealed unsafe class GpuPairedFASTQ : IEnumerable<(FastqRecord R1, FastqRe
         }
     }
 
+    /// <summary>One consensus read per overlapping pair (ppgpu.h "pair merge") on the device of ctx: set1 / set2 are
+    /// packed read sets with qualities, devRows the rows ppg_pairs_overlap wrote for the same maps, merged the
+    /// planes to write (Records = its record capacity, Qual may be null) of baseCap bases.  Every pointer is
+    /// caller device memory; MergeSize gives the capacities a merge needs.</summary>
+    public static PpgPairMergeResult Merge(nint ctx, PpgPackedView set1, PpgPackedView set2, long* devRec1, long* devRec2,
+        long npairs, void* devRows, PpgPackedView merged, long baseCap, long* devPairOf, long qualHi = 63, long qualLo = 47)
+    {
+        var m = new PpgPairMerge { QualHi = qualHi, QualLo = qualLo };
+        PpgPairMergeResult r;
+        PpGpu.Check(PpGpu.ppg_pair_merge_check(&m));
+        PpGpu.Check(PpGpu.ppg_pairs_merge(ctx, &m, &set1, &set2, devRec1, devRec2, npairs, devRows, npairs, merged.SeqOff,
+            merged.SeqLen, merged.Records, merged.Bases, merged.Mask, merged.Qual, baseCap, devPairOf, &r));
+        return r;
+    }
+
+    /// <summary>ppg_pairs_merge_size: the merged records and their padded bases for these rows.</summary>
+    public static (long Merged, long PaddedBases) MergeSize(nint ctx, PpgPackedView set1, PpgPackedView set2, long* devRec1,
+        long* devRec2, long npairs, void* devRows)
+    {
+        PpGpu.Check(PpGpu.ppg_pairs_merge_size(ctx, &set1, &set2, devRec1, devRec2, npairs, devRows, npairs, out long n,
+            out long b));
+        return (n, b);
+    }
+
     private sealed class File1
     {
         public nint Index, Shard;

@@ -177,7 +177,7 @@ public unsafe struct PpgPackedView      // ppg_packed_view: device pointers of a
     public uint* SeqLen;
     public uint* Bases;
     public uint* Mask;
-    public byte* Qual;                  // may be null; the overlap does not read it
+    public byte* Qual;                  // the overlap does not read it (may be null); the merge needs it
     public long Records;
 }
 
@@ -206,6 +206,35 @@ public unsafe struct PpgPairOverlapResult  // ppg_pair_overlap_result
     public long Mismatches;
     public fixed long Clipped[2];       // bases cut from R1 / R2
     public fixed long Reserved[5];
+}
+
+[StructLayout(LayoutKind.Sequential)]
+public unsafe struct PpgPairMerge       // ppg_pair_merge
+{
+    public long Flags;                  // 0
+    public long QualHi;                 // corrected: the taken base's quality byte is at least this (default 63) ...
+    public long QualLo;                 // ... and the overruled one's at most this (default 47)
+    public fixed long Reserved[5];      // 0
+}
+
+[StructLayout(LayoutKind.Sequential)]
+public unsafe struct PpgPairMergeResult // ppg_pair_merge_result
+{
+    public long Pairs;
+    public long Unmapped;
+    public long TooLong;
+    public long Unmerged;               // no overlap row
+    public long Stale;                  // a row that does not fit its pair
+    public long Merged;
+    public long MergedBases;
+    public long PaddedBases;            // seq_off[merged]
+    public long OverlapBases;           // positions both mates cover
+    public long Disagree;               // both bases, different
+    public long From2;                  // ... decided for read 2
+    public long Ties;                   // ... at equal quality (read 1 is taken)
+    public long NFilled;                // exactly one side N
+    public long NBoth;
+    public fixed long Corrected[2];     // read 1 / read 2 overruled across the thresholds
 }
 
 internal static unsafe class PpGpu
@@ -419,6 +448,16 @@ internal static unsafe class PpGpu
     [DllImport(Lib)] public static extern int ppg_pairs_overlap(nint ctx, void* overlap, void* set1, void* set2,
         long* devRec1, long* devRec2, long npairs, void* devRows, long rowCap, uint* devFoundMask, long maskCap,
         void* devWindows1, long winCap1, void* devWindows2, long winCap2, void* result, long* hist, long histCap);
+
+    // pair merge: one consensus read per overlapping pair as a third packed read set (merge: a PpgPairMerge*,
+    // set1 / set2: a PpgPackedView* with Qual, result: a PpgPairMergeResult*; the maps, rows and output planes are
+    // device pointers)
+    [DllImport(Lib)] public static extern int ppg_pair_merge_check(void* merge);
+    [DllImport(Lib)] public static extern int ppg_pairs_merge_size(nint ctx, void* set1, void* set2, long* devRec1,
+        long* devRec2, long npairs, void* devRows, long rowCap, out long merged, out long paddedBases);
+    [DllImport(Lib)] public static extern int ppg_pairs_merge(nint ctx, void* merge, void* set1, void* set2,
+        long* devRec1, long* devRec2, long npairs, void* devRows, long rowCap, long* devSeqOff, uint* devSeqLen,
+        long recCap, uint* devBases, uint* devMask, byte* devQual, long baseCap, long* devPairOf, void* result);
 
     [DllImport(Lib)] public static extern nint ppg_version();
     [DllImport(Lib)] public static extern nint ppg_build_id();

@@ -1090,6 +1090,111 @@ def pair_overlap(packed1, packed2, overlap, rec1=None, rec2=None, windows1=None,
     return PairOverlapResult(res, hist, rows, None if found_mask is None else found_mask.view(torch.uint32), wins[0], wins[1])
 
 
+class PairMerge:
+    """A pair merge (include/ppgpu.h "pair merge"): one consensus read per overlapping pair.  qual_hi / qual_lo are
+    quality bytes as they stand in the file; a disagreement counts as corrected when the base taken has at least
+    qual_hi and the one overruled at most qual_lo.  The defaults are '?' and '/': phred 30 and 14 at offset 33."""
+
+    def __init__(self, qual_hi=63, qual_lo=47):
+        self.qual_hi, self.qual_lo = qual_hi, qual_lo
+
+    def struct(self):
+        """The ppg_pair_merge of this merge; ValueError when ppg_pair_merge_check refuses it."""
+        m = _lib.PpgPairMerge(0, int(self.qual_hi), int(self.qual_lo), (C.c_int64 * 5)())
+        if lib.ppg_pair_merge_check(C.byref(m)) != 0:
+            raise ValueError(f"PairMerge: not a valid merge: {self!r}")
+        return m
+
+    def __repr__(self):
+        return f"PairMerge(qual_hi={self.qual_hi}, qual_lo={self.qual_lo})"
+
+
+class PairMergeResult:
+    """The result of a pair merge (include/ppgpu.h "pair merge"): the totals `pairs`, `unmapped`, `too_long`,
+    `unmerged`, `stale`, `merged`, `merged_bases`, `padded_bases`, `overlap_bases`, `disagree`, `from2`, `ties`,
+    `n_filled`, `n_both` and `agree` (the overlap's other positions); `corrected` (read 1 overruled, read 2
+    overruled); `reads`, the merged set as a PackedReads of CUDA tensors whose `records` and `total_bases` are the
+    merged ones, so that to_host() cuts exactly; `pair_of` (int64 CUDA tensor: the pair of each merged record, or
+    None); `overlap`, the PairOverlapResult when PairedFASTQ.Merge ran the overlap."""
+
+    TOTALS = ("pairs", "unmapped", "too_long", "unmerged", "stale", "merged", "merged_bases", "padded_bases",
+              "overlap_bases", "disagree", "from2", "ties", "n_filled", "n_both")
+
+    def __init__(self, result, reads, pair_of=None, overlap=None):
+        for name in self.TOTALS:
+            setattr(self, name, int(getattr(result, name)))
+        self.corrected = tuple(int(x) for x in result.corrected)
+        self.reads, self.pair_of, self.overlap = reads, pair_of, overlap
+
+    @property
+    def agree(self):
+        return self.overlap_bases - self.disagree - self.n_filled - self.n_both
+
+    def __repr__(self):
+        return (f"PairMergeResult(pairs={self.pairs}, merged={self.merged}, merged_bases={self.merged_bases}, "
+                f"disagree={self.disagree}, corrected={self.corrected})")
+
+
+def pair_merge(packed1, packed2, rows, merge=None, rec1=None, rec2=None, out=None, quality=True, pair_of=True, device=None):
+    """The pair merge of two packed read sets with qualities on one GPU (ppg_pairs_merge), as a PairMergeResult.
+    rows: the int32 CUDA tensor [pairs, 4] a pair_overlap of the same sets and maps wrote (a zeroed row leaves its
+    pair out).  merge: a PairMerge (None: the defaults).  rec1 / rec2: as in pair_overlap.  out: a PackedReads of
+    CUDA tensors to write (None: sized with ppg_pairs_merge_size and allocated, with a quality plane iff
+    `quality`).  pair_of: True allocates, an int64 CUDA tensor is written, False / None leaves it out.  Ordered
+    after torch's stream, complete on return."""
+    import torch
+    what = "pair_merge"
+    for p in (packed1, packed2):
+        if not isinstance(p, PackedReads) or not p.on_device:
+            raise ValueError(f"{what}: expected two PackedReads of CUDA tensors")
+        p._check_device(what)
+        if p.qual is None:
+            raise ValueError(f"{what}: both read sets need their quality plane")
+    tdev = packed1.seq_off.device
+    if packed2.seq_off.device != tdev:
+        raise ValueError(f"{what}: both read sets must be on one device")
+    dev = device or Device.default(tdev.index if tdev.index is not None else torch.cuda.current_device())
+    m = merge.struct() if isinstance(merge, PairMerge) else PairMerge().struct() if merge is None else merge
+    if not isinstance(m, _lib.PpgPairMerge):
+        raise ValueError(f"{what}: expected a PairMerge")
+    maps = [None if r is None else _int_tensor_arg(r, (torch.int64,), what, "rec1 / rec2") for r in (rec1, rec2)]
+    if maps[0] is not None and maps[1] is not None and maps[0].numel() != maps[1].numel():
+        raise ValueError(f"{what}: rec1 and rec2 differ in length")
+    given = [r.numel() for r in maps if r is not None]
+    npairs = given[0] if given else min(packed1.records, packed2.records)
+    _int_tensor_arg(rows, (torch.int32,), what, "rows")
+    if rows.numel() % 4:
+        raise ValueError(f"{what}: rows must hold four int32 per pair")
+    views = [_lib.PpgPackedView(p.seq_off.data_ptr(), p.seq_len.data_ptr(), p.bases.data_ptr(), p.mask.data_ptr(),
+                                p.qual.data_ptr(), p.records) for p in (packed1, packed2)]
+    ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None and t.numel() else None   # noqa: E731
+    inputs = (C.byref(views[0]), C.byref(views[1]), ptr(maps[0]), ptr(maps[1]), npairs, ptr(rows), rows.numel() // 4)
+    dev.after_torch()
+    if out is None:
+        nrec, nbases = C.c_int64(), C.c_int64()
+        check(lib.ppg_pairs_merge_size(dev.handle, *inputs, C.byref(nrec), C.byref(nbases)), what)
+        out = PackedReads.empty(nrec.value, nbases.value, quality, tdev)
+        dev.after_torch()   # (the planes' zeroing)
+    elif not isinstance(out, PackedReads) or not out.on_device:
+        raise ValueError(f"{what}: out must be a PackedReads of CUDA tensors")
+    else:
+        out._check_device(what)
+    if pair_of is True:
+        pair_of = torch.zeros(out.rec_cap, dtype=torch.int64, device=tdev)
+        dev.after_torch()
+    elif pair_of is False:
+        pair_of = None
+    if pair_of is not None:
+        _int_tensor_arg(pair_of, (torch.int64,), what, "pair_of")
+        if pair_of.numel() < out.rec_cap:
+            raise ValueError(f"{what}: pair_of is shorter than out's records")
+    res = _lib.PpgPairMergeResult()
+    check(lib.ppg_pairs_merge(dev.handle, C.byref(m), *inputs, *out._ptrs(),
+                              C.c_void_p(pair_of.data_ptr()) if pair_of is not None else None, C.byref(res)), what)
+    out.records, out.total_bases = int(res.merged), int(res.padded_bases)
+    return PairMergeResult(res, out, None if pair_of is None else pair_of[:int(res.merged)])
+
+
 class SelectedRecords:
     """The records a mask selects (include/ppgpu.h "record selection"): `bytes` (uint8, the selected
     records' text back to back), `sel_off` (int64, records + 1 offsets into it), `desc` (records x 4:

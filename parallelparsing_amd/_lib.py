@@ -179,6 +179,9 @@ _SIGS = {
     "ppg_pairs_emit_stats": (C.c_int, [vp, P(C.c_double), i32]),
     "ppg_pair_overlap_check": (C.c_int, [vp]),
     "ppg_pairs_overlap": (C.c_int, [vp, vp, vp, vp, vp, vp, i64, vp, i64, vp, i64, vp, i64, vp, i64, vp, vp, i64]),
+    "ppg_pair_merge_check": (C.c_int, [vp]),
+    "ppg_pairs_merge_size": (C.c_int, [vp, vp, vp, vp, vp, i64, vp, i64, P(i64), P(i64)]),
+    "ppg_pairs_merge": (C.c_int, [vp, vp, vp, vp, vp, vp, i64, vp, i64, vp, vp, i64, vp, vp, vp, i64, vp, vp]),
 }
 
 
@@ -283,6 +286,19 @@ class PpgPairOverlapResult(C.Structure):
 
 
 PPG_OVERLAP_MAX_LEN, PPG_OVERLAP_HIST = 1024, 2048
+
+
+class PpgPairMerge(C.Structure):
+    """ppg_pair_merge (include/ppgpu.h)."""
+    _fields_ = [("flags", C.c_int64), ("qual_hi", C.c_int64), ("qual_lo", C.c_int64), ("reserved", C.c_int64 * 5)]
+
+
+class PpgPairMergeResult(C.Structure):
+    """ppg_pair_merge_result (include/ppgpu.h)."""
+    _fields_ = [("pairs", C.c_int64), ("unmapped", C.c_int64), ("too_long", C.c_int64), ("unmerged", C.c_int64),
+                ("stale", C.c_int64), ("merged", C.c_int64), ("merged_bases", C.c_int64), ("padded_bases", C.c_int64),
+                ("overlap_bases", C.c_int64), ("disagree", C.c_int64), ("from2", C.c_int64), ("ties", C.c_int64),
+                ("n_filled", C.c_int64), ("n_both", C.c_int64), ("corrected", C.c_int64 * 2)]
 
 
 for _name, (_res, _args) in _SIGS.items():

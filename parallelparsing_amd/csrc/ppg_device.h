@@ -166,6 +166,24 @@ struct PpgPairOverlap {
 // insert-size histogram of kPoHist bins.  kPoMaxLen: the longest read a pair is analysed with.
 constexpr int kPoAcc = 16, kPoHist = 2048, kPoMaxLen = 1024;
 
+// a ppg_pair_merge (include/ppgpu.h "pair merge") as the merge's arguments
+struct PpgPairMerge {
+    int64_t flags, qual_hi, qual_lo, reserved[5];
+};
+// the pair merge's accumulators: the int64 fields of a ppg_pair_merge_result in order (pairs, unmapped, too_long,
+// unmerged, stale, merged, merged_bases, padded_bases: ppg_pm_place; overlap_bases, disagree, from2, ties,
+// n_filled, n_both, corrected[2]: ppg_pm_emit)
+constexpr int kPmAcc = 16, kPmPlaceAcc = 8;
+constexpr int kPmTile = 256;   // pairs per block of ppg_pm_count and ppg_pm_place
+// ppg_pm_place -> ppg_pm_emit, per merged record: the first 32-base units of both reads in their sets, their
+// lengths and the row's d, all checked (the merged length is L2 + d)
+struct alignas(16) PpgMergeRec {
+    int64_t u1, u2;
+    uint32_t L1, L2;
+    int32_t d;
+    uint32_t pad;
+};
+
 // ppg_sel_copy: the destination bytes one workgroup writes (256 threads x 4 words of 16 B); ppg_sel_place
 // records, per multiple of it inside a batch's destination range, the selected record that holds that byte
 constexpr uint32_t kSelSpan = 16384;

@@ -115,6 +115,7 @@ struct ppg_ctx {
     uint8_t *stage = nullptr;           // pinned device -> host staging (CreateIndex windows), kept across calls
     size_t stage_n = 0;
     int overlap_grid = 0;               // ppg_po_overlap's grid (0: the default; the tests force small ones)
+    int merge_grid = 0;                 // ppg_pm_emit's grid, likewise
 };
 
 template <class T>

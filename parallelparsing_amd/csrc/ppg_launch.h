@@ -143,6 +143,24 @@ PPG_WEAK hipError_t ppg_launch_pair_overlap(hipStream_t s, const PpgPackedView &
                                             const PpgPairOverlap *po, int32_t *rows, uint32_t *found, uint32_t *win1,
                                             uint32_t *win2, uint64_t *acc, int blocks, int cus);
 
+// ---- ppg_pairmerge.hip ----
+// Weak for the same reason (pairmerge_linked, ppg_stages.cpp).  Two packed read sets with qualities and the
+// overlap's rows; trec / tbase: a value per tile of kPmTile pairs, rbase / bbase: one more; host_totals:
+// two values in pinned memory; recs: a row per merged record; acc: kPmAcc values.
+PPG_WEAK hipError_t ppg_launch_pm_count(hipStream_t s, const PpgPackedView &s1, const PpgPackedView &s2,
+                                        const int64_t *rec1, const int64_t *rec2, int64_t npairs, const int32_t *rows,
+                                        uint64_t *trec, uint64_t *tbase);
+PPG_WEAK hipError_t ppg_launch_pm_scan(hipStream_t s, const uint64_t *trec, const uint64_t *tbase, uint64_t *rbase,
+                                       uint64_t *bbase, int64_t *host_totals, int ntiles);
+PPG_WEAK hipError_t ppg_launch_pm_place(hipStream_t s, const PpgPackedView &s1, const PpgPackedView &s2,
+                                        const int64_t *rec1, const int64_t *rec2, int64_t npairs, const int32_t *rows,
+                                        const uint64_t *rbase, const uint64_t *bbase, int64_t *seq_off,
+                                        uint32_t *seq_len, int64_t *pair_of, PpgMergeRec *recs, uint64_t *acc);
+PPG_WEAK hipError_t ppg_launch_pm_emit(hipStream_t s, const PpgPackedView &s1, const PpgPackedView &s2,
+                                       const PpgMergeRec *recs, const int64_t *seq_off, int64_t merged,
+                                       int64_t padded_bases, const PpgPairMerge *pm, uint32_t *bases, uint32_t *mask,
+                                       uint8_t *qual, uint64_t *acc, int blocks, int cus);
+
 // ---- ppg_seqselect.hip ----
 // Weak for the same reason (select_linked, ppg_stages.cpp).
 PPG_WEAK hipError_t ppg_launch_sel_count(hipStream_t s, const PpgBatchView &v, const uint32_t *mask, uint64_t bit0,

@@ -4,7 +4,8 @@
 // (ppg_readprofile.hip) and record selection (ppg_seqselect.hip): for each its
 // pieces on one batch, its C entry points (one-shot on a one-batch shard, the hook of every batch of a
 // run, and what the last run left) and the measurement hook of its tools/*_probe.py.  The pair overlap
-// (ppg_pairoverlap.hip) is here as well: it has no batch, it reads two packed read sets the pack stage wrote.
+// (ppg_pairoverlap.hip) is here as well: it has no batch, it reads two packed read sets the pack stage wrote; so is
+// the pair merge (ppg_pairmerge.hip), which makes a third packed read set from those two and the overlap's rows.
 //
 // A batch's hooks run from one place, shard_batch_hooks, called once by batch_collect (ppg_api.cpp).  The
 // unit kernels of query, filter, trim, dedup and profile read one layout of the batch (StageLayout, ppg_host.h), which
@@ -27,7 +28,8 @@ static_assert(sizeof(ppg_seq_query_result) == 8 * 8 && sizeof(ppg_read_filter_re
                   sizeof(ppg_read_dedup_result) == 8 * kDdAcc && sizeof(ppg_read_dedup) == sizeof(PpgReadDedup) &&
                   sizeof(ppg_pair_overlap_result) == 8 * kPoAcc && sizeof(ppg_pair_overlap) == sizeof(PpgPairOverlap) &&
                   sizeof(ppg_packed_view) == sizeof(PpgPackedView) && PPG_OVERLAP_MAX_LEN == kPoMaxLen &&
-                  PPG_OVERLAP_HIST == kPoHist,
+                  PPG_OVERLAP_HIST == kPoHist && sizeof(ppg_pair_merge_result) == 8 * kPmAcc &&
+                  sizeof(ppg_pair_merge) == sizeof(PpgPairMerge) && sizeof(ppg_pair_merge) == 64 && sizeof(PpgMergeRec) == 32,
               "a stage's result struct is its accumulators");
 
 static bool seq_linked() {   // (weak references, ppg_launch.h: absent from the host-only sanitizer build)
@@ -438,6 +440,66 @@ static int pairoverlap_args(ppg_ctx *ctx, const void *overlap, const void *set1,
     if ((rows && npairs > row_cap) || (found && npairs > mask_cap) || (win1 && a.s1.records > win_cap1) ||
         (win2 && a.s2.records > win_cap2) || (hist && hist_cap < kPoHist))
         return PPG_BUF_ERROR;
+    return PPG_OK;
+}
+
+// ---- pair merge (ppg_pairmerge.hip) ----
+// As the overlap: two packed read sets in caller memory, on the ctx stream; the output is a third.
+static bool pairmerge_linked() {
+    return ppg_launch_pm_count && ppg_launch_pm_scan && ppg_launch_pm_place && ppg_launch_pm_emit;
+}
+
+// the rules of include/ppgpu.h "pair merge"; host only
+static bool pairmerge_ok(const void *merge, PpgPairMerge *out) {
+    if (!merge) return false;
+    PpgPairMerge m;
+    memcpy(&m, merge, sizeof m);
+    if (m.flags != 0 || m.qual_lo < 0 || m.qual_hi > 255 || m.qual_lo >= m.qual_hi) return false;
+    for (int64_t r : m.reserved)
+        if (r != 0) return false;
+    if (out) *out = m;
+    return true;
+}
+
+struct PairMergeArgs {
+    PpgPairMerge pm;
+    PpgPackedView s1, s2;
+    int ntiles;
+};
+
+// PPG_ARG_ERROR of both merge entry points for the inputs (and PPG_BUF_ERROR for the rows), before anything runs
+static int pairmerge_inputs(ppg_ctx *ctx, const void *set1, const void *set2, const int64_t *rec1, const int64_t *rec2,
+                            int64_t npairs, const void *rows, int64_t row_cap, bool quals, PairMergeArgs &a) {
+    if (!ctx || !packed_view_ok(set1, &a.s1) || !packed_view_ok(set2, &a.s2)) return PPG_ARG_ERROR;
+    if (quals && (!a.s1.qual || !a.s2.qual || ((uintptr_t)a.s1.qual & 15) || ((uintptr_t)a.s2.qual & 15))) return PPG_ARG_ERROR;
+    if (npairs < 0 || row_cap < 0 || (!rows && npairs > 0) || npairs > (int64_t)kPmTile * INT32_MAX) return PPG_ARG_ERROR;
+    if (((uintptr_t)rec1 & 7) || ((uintptr_t)rec2 & 7) || ((uintptr_t)rows & 15)) return PPG_ARG_ERROR;
+    if ((!rec1 && npairs > a.s1.records) || (!rec2 && npairs > a.s2.records)) return PPG_ARG_ERROR;   // the identity map
+    if (npairs > row_cap) return PPG_BUF_ERROR;
+    a.ntiles = (int)((npairs + kPmTile - 1) / kPmTile);
+    return PPG_OK;
+}
+
+// the merge's scratch: per tile of pairs the merged records and padded bases and their scans, the totals in
+// pinned memory, a PpgMergeRec per merged record, the accumulators
+struct PairMergeScratch {
+    DevBuf<uint64_t> tiles, acc;
+    DevBuf<PpgMergeRec> recs;
+    PinnedBuf host;
+    uint64_t *trec(int) { return tiles.p; }
+    uint64_t *tbase(int n) { return tiles.p + (size_t)n + 1; }
+    uint64_t *rbase(int n) { return tiles.p + 2 * ((size_t)n + 1); }
+    uint64_t *bbase(int n) { return tiles.p + 3 * ((size_t)n + 1); }
+};
+
+// count and scan, queued on s; the totals are in w.host once s has been synchronised
+static int pairmerge_count(hipStream_t s, const PairMergeArgs &a, const int64_t *rec1, const int64_t *rec2, int64_t npairs,
+                           const void *rows, PairMergeScratch &w) {
+    const int n = a.ntiles;
+    HIPCHK(w.tiles.alloc(4 * ((size_t)n + 1)));
+    HIPCHK(w.host.alloc(16));
+    HIPCHK(ppg_launch_pm_count(s, a.s1, a.s2, rec1, rec2, npairs, (const int32_t *)rows, w.trec(n), w.tbase(n)));
+    HIPCHK(ppg_launch_pm_scan(s, w.trec(n), w.tbase(n), w.rbase(n), w.bbase(n), (int64_t *)w.host.p, n));
     return PPG_OK;
 }
 
@@ -968,6 +1030,62 @@ int ppg_pairs_overlap(ppg_ctx *ctx, const void *overlap, const void *set1, const
     return PPG_OK;
 }
 
+// ---- pair merge: blocking calls on the ctx stream ----
+int ppg_pair_merge_check(const void *merge) { return pairmerge_ok(merge, nullptr) ? PPG_OK : PPG_ARG_ERROR; }
+
+int ppg_pairs_merge_size(ppg_ctx *ctx, const void *set1, const void *set2, const int64_t *dev_rec1, const int64_t *dev_rec2,
+                         int64_t npairs, const void *dev_rows, int64_t row_cap, int64_t *merged, int64_t *padded_bases) {
+    PairMergeArgs a;
+    if (int rc = pairmerge_inputs(ctx, set1, set2, dev_rec1, dev_rec2, npairs, dev_rows, row_cap, false, a)) return rc;
+    if (!pairmerge_linked()) return PPG_UNSUPPORTED;
+    HIPCHK(hipSetDevice(ctx->device));
+    PairMergeScratch w;
+    if (int rc = pairmerge_count(ctx->stream, a, dev_rec1, dev_rec2, npairs, dev_rows, w)) return rc;
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    if (merged) *merged = ((volatile int64_t *)w.host.p)[0];
+    if (padded_bases) *padded_bases = ((volatile int64_t *)w.host.p)[1];
+    return PPG_OK;
+}
+
+int ppg_pairs_merge(ppg_ctx *ctx, const void *merge, const void *set1, const void *set2, const int64_t *dev_rec1,
+                    const int64_t *dev_rec2, int64_t npairs, const void *dev_rows, int64_t row_cap, int64_t *dev_seq_off,
+                    uint32_t *dev_seq_len, int64_t rec_cap, uint32_t *dev_bases, uint32_t *dev_mask, uint8_t *dev_qual,
+                    int64_t base_cap, int64_t *dev_pair_of, void *result) {
+    PairMergeArgs a;
+    if (!pairmerge_ok(merge, &a.pm)) return PPG_ARG_ERROR;
+    // the output planes, as ppg_shard_pack_seq takes them
+    // (a plane of capacity 0 holds nothing and may be NULL: an allocator gives no address for no bytes)
+    if (rec_cap < 0 || base_cap < 0 || base_cap % 32 != 0 || !dev_seq_off || (!dev_seq_len && rec_cap > 0) ||
+        ((!dev_bases || !dev_mask) && base_cap > 0) ||
+        ((uintptr_t)dev_seq_off & 7) || ((uintptr_t)dev_seq_len & 3) || ((uintptr_t)dev_bases & 7) || ((uintptr_t)dev_mask & 3) ||
+        ((uintptr_t)dev_qual & 15) || ((uintptr_t)dev_pair_of & 7))
+        return PPG_ARG_ERROR;
+    if (int rc = pairmerge_inputs(ctx, set1, set2, dev_rec1, dev_rec2, npairs, dev_rows, row_cap, true, a)) return rc;
+    if (!pairmerge_linked()) return PPG_UNSUPPORTED;
+    HIPCHK(hipSetDevice(ctx->device));
+    hipStream_t s = ctx->stream;
+    int cus = 0;
+    HIPCHK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, ctx->device));
+    PairMergeScratch w;
+    if (int rc = pairmerge_count(s, a, dev_rec1, dev_rec2, npairs, dev_rows, w)) return rc;
+    HIPCHK(hipStreamSynchronize(s));
+    const int64_t merged = ((volatile int64_t *)w.host.p)[0], padded = ((volatile int64_t *)w.host.p)[1];
+    if (merged > rec_cap || padded > base_cap) return PPG_BUF_ERROR;   // before the writers: nothing is written
+    HIPCHK(w.acc.alloc(kPmAcc));
+    HIPCHK(w.recs.alloc((size_t)merged));
+    HIPCHK(hipMemsetAsync(w.acc.p, 0, 8 * (size_t)kPmAcc, s));
+    if (npairs == 0) HIPCHK(hipMemsetAsync(dev_seq_off, 0, 8, s));   // (else ppg_pm_place writes seq_off[merged])
+    HIPCHK(ppg_launch_pm_place(s, a.s1, a.s2, dev_rec1, dev_rec2, npairs, (const int32_t *)dev_rows, w.rbase(a.ntiles),
+                               w.bbase(a.ntiles), dev_seq_off, dev_seq_len, dev_pair_of, w.recs.p, w.acc.p));
+    HIPCHK(ppg_launch_pm_emit(s, a.s1, a.s2, w.recs.p, dev_seq_off, merged, padded, &a.pm, dev_bases, dev_mask, dev_qual,
+                              w.acc.p, ctx->merge_grid, cus));
+    int64_t h[kPmAcc];
+    HIPCHK(hipMemcpyAsync(h, w.acc.p, sizeof h, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    if (result) memcpy(result, h, sizeof(ppg_pair_merge_result));
+    return PPG_OK;
+}
+
 // ---- record selection: the sequence queries entry points' counterparts ----
 static bool select_bufs_ok(const int64_t *recno, const int64_t *sel_off, const uint32_t *desc, int64_t sel_cap,
                            const uint8_t *bytes, int64_t byte_cap) {
@@ -1385,6 +1503,60 @@ int ppgx_pairoverlap_times(ppg_ctx *ctx, const void *overlap, const void *set1, 
 int ppgx_pairoverlap_grid(ppg_ctx *ctx, int blocks) {
     if (!ctx || blocks < 0) return PPG_ARG_ERROR;
     ctx->overlap_grid = blocks;
+    return PPG_OK;
+}
+
+// tools/pairmerge_probe.py.  Pairs (i, i) of the two sets with the rows dev_rows, into planes of the hook's own.
+// ms[0]: count and scan; ms[1]: place, with the zeroing of the accumulators; ms[2] / ms[3]: the emit kernel with /
+// without the output's qual plane.  sizes[0..1]: the merged records and their padded bases.  The stream is the ctx's.
+int ppgx_pairmerge_times(ppg_ctx *ctx, const void *merge, const void *set1, const void *set2, int64_t npairs,
+                         const void *dev_rows, int reps, float *ms, int64_t *sizes) {
+    PairMergeArgs a;
+    if (!ms || !sizes || reps < 1 || !pairmerge_ok(merge, &a.pm)) return PPG_ARG_ERROR;
+    if (int rc = pairmerge_inputs(ctx, set1, set2, nullptr, nullptr, npairs, dev_rows, npairs, true, a)) return rc;
+    if (!pairmerge_linked()) return PPG_UNSUPPORTED;
+    HIPCHK(hipSetDevice(ctx->device));
+    hipStream_t s = ctx->stream;
+    int cus = 0;
+    HIPCHK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, ctx->device));
+    PairMergeScratch w;
+    if (int rc = pairmerge_count(s, a, nullptr, nullptr, npairs, dev_rows, w)) return rc;
+    HIPCHK(hipStreamSynchronize(s));
+    const int64_t merged = sizes[0] = ((volatile int64_t *)w.host.p)[0], padded = sizes[1] = ((volatile int64_t *)w.host.p)[1];
+    DevBuf<int64_t> off;
+    DevBuf<uint32_t> len, bases, mask;
+    DevBuf<uint8_t> qual;
+    HIPCHK(w.acc.alloc(kPmAcc));
+    HIPCHK(w.recs.alloc((size_t)merged));
+    HIPCHK(off.alloc((size_t)merged + 1));
+    HIPCHK(len.alloc((size_t)merged));
+    HIPCHK(bases.alloc((size_t)padded / 16));
+    HIPCHK(mask.alloc((size_t)padded / 32));
+    HIPCHK(qual.alloc((size_t)padded));
+    HIPCHK(hipMemsetAsync(off.p, 0, 8, s));
+    const int n = a.ntiles;
+    return time_steps(s, 4, reps, ms, [&](int step) {
+        hipError_t e = hipSuccess;
+        switch (step) {
+            case 0:
+                e = ppg_launch_pm_count(s, a.s1, a.s2, nullptr, nullptr, npairs, (const int32_t *)dev_rows, w.trec(n), w.tbase(n));
+                return e != hipSuccess ? e : ppg_launch_pm_scan(s, w.trec(n), w.tbase(n), w.rbase(n), w.bbase(n), (int64_t *)w.host.p, n);
+            case 1:
+                e = hipMemsetAsync(w.acc.p, 0, 8 * (size_t)kPmAcc, s);
+                return e != hipSuccess ? e
+                                       : ppg_launch_pm_place(s, a.s1, a.s2, nullptr, nullptr, npairs, (const int32_t *)dev_rows,
+                                                             w.rbase(n), w.bbase(n), off.p, len.p, nullptr, w.recs.p, w.acc.p);
+            default:
+                return ppg_launch_pm_emit(s, a.s1, a.s2, w.recs.p, off.p, merged, padded, &a.pm, bases.p, mask.p,
+                                          step == 2 ? qual.p : nullptr, w.acc.p, ctx->merge_grid, cus);
+        }
+    });
+}
+
+// ppg_pm_emit's grid on this ctx from now on (0: the default).  The tests force one block and uneven shares with it.
+int ppgx_pairmerge_grid(ppg_ctx *ctx, int blocks) {
+    if (!ctx || blocks < 0) return PPG_ARG_ERROR;
+    ctx->merge_grid = blocks;
     return PPG_OK;
 }
 

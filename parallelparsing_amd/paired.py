@@ -17,7 +17,7 @@ import ctypes as C
 
 import numpy as np
 
-from . import Device, IndexIO, PackedReads, PairOverlap, Shard, pair_overlap, records_from_descriptors
+from . import Device, IndexIO, PackedReads, PairOverlap, Shard, pair_merge, pair_overlap, records_from_descriptors
 from ._lib import lib, check, PpgPairResult
 
 DUP = -2      # key of a record parsed twice (Q1), dropped before pairing
@@ -203,14 +203,14 @@ class PairedFASTQ:
     def chunks(self):
         return (self.pairs + self.K - 1) // self.K
 
-    def _packed(self, f):
-        """File f's reads packed without qualities, as a PackedReads on the device: one call on a one-batch
-        shard, the pack hook and a re-run on a multi-batch one (whose output does not stay resident)."""
+    def _packed(self, f, quality=False):
+        """File f's reads packed (without qualities unless asked), as a PackedReads on the device: one call on a
+        one-batch shard, the pack hook and a re-run on a multi-batch one (whose output does not stay resident)."""
         sh = self.shards[f]
         if sh.batches == 1:
-            return sh.pack_sequences(quality=False)
+            return sh.pack_sequences(quality=quality)
         tot, rec = sh.seq_bases()
-        packed = PackedReads.empty(rec, tot, False, self.dev.device)
+        packed = PackedReads.empty(rec, tot, quality, self.dev.device)
         sh.set_seqpack(packed).run()
         ok = sh.seqpack_ready
         sh.set_seqpack(None)
@@ -233,6 +233,21 @@ class PairedFASTQ:
         w = True if windows else None
         return pair_overlap(packed[0], packed[1], overlap if overlap is not None else PairOverlap(), maps[0], maps[1],
                             windows1=w, windows2=w, device=self.dev)
+
+    def Merge(self, overlap=None, merge=None):
+        """One consensus read per overlapping pair (include/ppgpu.h "pair merge"), as a PairMergeResult whose
+        `overlap` is the PairOverlapResult it was made from.  Both files are packed with qualities on the device,
+        the overlap runs with the pairing's maps as in Overlap() (no windows), then the merge with its rows.
+        overlap: a PairOverlap (None: fastp's defaults); merge: a PairMerge (None: the defaults)."""
+        import torch
+        packed = [self._packed(f, quality=True) for f in (0, 1)]
+        tdev = torch.device("cuda", self.dev.device)
+        maps = [torch.from_numpy(np.ascontiguousarray(self._pairs.records(f, 0, self.pairs))).to(tdev) for f in (0, 1)]
+        ov = pair_overlap(packed[0], packed[1], overlap if overlap is not None else PairOverlap(), maps[0], maps[1],
+                          found_mask=False, device=self.dev)
+        r = pair_merge(packed[0], packed[1], ov.rows, merge, maps[0], maps[1], device=self.dev)
+        r.overlap = ov
+        return r
 
     def pair_chunks(self):
         """Yield (j, R1 records, R2 records) for every pair chunk in order."""
