@@ -1163,6 +1163,104 @@ int ppg_pairs_merge(ppg_ctx *ctx, const void *merge, const void *set1, const voi
                     int64_t *dev_seq_off, uint32_t *dev_seq_len, int64_t rec_cap, uint32_t *dev_bases,
                     uint32_t *dev_mask, uint8_t *dev_qual, int64_t base_cap, int64_t *dev_pair_of, void *result);
 
+/* ---- k-mer counts: the k-mer spectrum and the most frequent k-mers of a packed read set ----
+ * The one report of a QC tool that looks across reads below the read: FastQC's "Kmer Content" and
+ * "Overrepresented sequences", and the spectrum Jellyfish or KMC computes first for genome size, coverage, error
+ * rate and contamination.  It works on one packed read set ("packed reads" above), so a k-mer is a shift and a
+ * mask of resident words, and chains with the record stages through their mask and windows.  The reference has
+ * nothing of the kind; the semantics are this library's, in exact integers.
+ * Parameters.  A ppg_kmer_count: eight int64_t, 64 bytes, passed as const void *.  1 <= k <= 31; flags a
+ * combination of PPG_KMER_CANONICAL, PPG_KMER_USE_WINDOWS, PPG_KMER_USE_MASK, PPG_KMER_ACCUMULATE; reserved 0.
+ * ppg_kmer_count_check is host only: PPG_ARG_ERROR for a NULL struct, unknown flag bits, k out of range or a
+ * non-zero reserved field, PPG_OK otherwise; every entry point that takes the struct applies it.
+ * Input.  The set as a ppg_packed_view, declared in "pair overlap" above: qual may be NULL and is not read; fewer
+ * than 2^32 - 1 records.  dev_mask: the hit-mask format indexed by record, mask_cap a multiple of 32; required with
+ * USE_MASK and NULL without it.  dev_windows: the trim's row format, windows_cap rows, 8-byte aligned; required
+ * with USE_WINDOWS and NULL without it.  A record participates when its mask bit is set or USE_MASK is off.  The
+ * window (s, w) of a record of length L is (0, L) without USE_WINDOWS; with it the row (start, len) is clamped as
+ * in the profile: s = min(start, L), w = min(len, L - s).  No row makes a kernel read outside the record's planes.
+ * Both inputs are only read.
+ * K-mers.  For a participating record every start p with s <= p and p + k <= s + w is a position.  A position is
+ * valid when none of the mask-plane bits of bases p .. p + k - 1 is set: N, lower case and a CRLF file's '\r'
+ * break k-mers, as they are mismatches elsewhere.  The key of the word x_0 .. x_{k-1} with 2-bit codes c_i is
+ *   K(x) = sum of c_i * 4^(k - 1 - i):
+ * the first base is most significant, so unsigned order is lexicographic order with A < C < G < T.  With
+ * CANONICAL the key is min(K(x), K(revcomp x)), where revcomp x has the codes 3 - c_{k-1-i}.  A key never equals
+ * the empty marker below: k <= 31 leaves the top two bits clear.
+ * Table.  dev_table: caller device memory, 16-byte aligned, `slots` rows of two uint64 {key, count}; slots a
+ * power of two, at least 64.  An empty row is {~0, 0}.  The home of a key is mix(key) >> (64 - log2 slots) with
+ * the mix of "read dedup" above; probing is linear with wrap, so a consumer can probe the table itself.  Without
+ * ACCUMULATE the call first makes the whole table empty; with it the call adds to what an earlier call with the
+ * same k and CANONICAL bit left there (the caller guarantees that they match).  After a call that returns PPG_OK
+ * every distinct key ever inserted has exactly one row, which holds the number of valid positions with that
+ * key, and every other row is empty.  Which row holds a key is unspecified; the set of rows is a function of the
+ * inputs alone.
+ * Capacity.  PPG_OK requires that the occupied rows after the call are at most slots / 2.  Otherwise the call
+ * returns PPG_BUF_ERROR; the table's contents are then unspecified, and nothing outside it is written (result
+ * and spectrum included).  Nobody knows the distinct count in advance, so an undersized table is a normal call
+ * and fails fast: a device counter of claimed rows stops the inserts once it passes slots / 2, and every probe
+ * is bounded by `slots` steps.  A failing call costs about what a succeeding one costs; a caller sizes by
+ * doubling.
+ * Outputs, both optional and host memory.
+ *   result    a ppg_kmer_count_result, declared below: sixteen int64_t.
+ *   spectrum  int64, spectrum_cap >= PPG_KMER_SPECTRUM = 1024 entries, else PPG_BUF_ERROR before anything runs;
+ *             the first 1024 are written.  spectrum[0] = 0; spectrum[c] = the rows with count c for 1 <= c <=
+ *             1022; spectrum[1023] = the rows with count >= 1023.  It is made over the table after the call, so
+ *             it sums to `distinct`.
+ *  ppg_kmer_count_check  above.
+ *  ppg_kmers_count    the count, the totals and the spectrum.
+ *  ppg_kmers_select   the rows with count >= min_count (min_count >= 1, else PPG_ARG_ERROR) into dev_out: device
+ *                     memory, 16-byte aligned, out_cap rows of 16 bytes, in unspecified order; *found (optional)
+ *                     is their exact number.  When found > out_cap the call returns PPG_BUF_ERROR with *found
+ *                     set, the first out_cap rows unspecified and nothing past them written.  dev_out NULL with
+ *                     out_cap 0 only counts and returns PPG_OK.
+ *  ppg_kmers_lookup   dev_counts[i] (device int64, 8-byte aligned) = the count of dev_keys[i] (device uint64,
+ *                     8-byte aligned) as given -- a key is not canonicalised, that is the caller's job -- and
+ *                     0 for a key the table does not hold, ~0 among them.
+ * PPG_ARG_ERROR: a NULL ctx, view, view plane other than qual, or table; a negative count or cap; a misaligned
+ * pointer; a mask_cap that is no multiple of 32; slots not a power of two or below 64; a flag without its buffer
+ * or a buffer without its flag; a seq_off[records] that is negative or no multiple of 32.  PPG_BUF_ERROR: more
+ * records than mask_cap or windows_cap, a spectrum_cap below 1024.  Nothing is written on either.  The calls run
+ * on the ctx stream and block, like the other one-shot calls; the caller orders the producers of the planes, the
+ * mask and the windows before them with ppg_ctx_wait_stream.
+ * Not built: k > 31 (a key of more than one word); minimizer or super-k-mer partitioning; counts across ranks (a
+ * rank's table sees its own share); a per-batch shard hook or a cursor (a multi-batch shard leaves its whole
+ * packed set resident through ppg_shard_set_seqpack, which is what the Python layer counts); quality-aware
+ * k-mers; writing the table to a Jellyfish or KMC file. */
+enum { PPG_KMER_CANONICAL = 1, PPG_KMER_USE_WINDOWS = 2, PPG_KMER_USE_MASK = 4, PPG_KMER_ACCUMULATE = 8 };
+enum { PPG_KMER_SPECTRUM = 1024 };
+typedef struct {
+    int64_t flags;           /* PPG_KMER_* */
+    int64_t k;               /* 1 .. 31 */
+    int64_t reserved[6];     /* 0 */
+} ppg_kmer_count;
+typedef struct {
+    /* of this call */
+    int64_t records;         /* the set's records */
+    int64_t participating;
+    int64_t short_reads;     /* participants with w < k */
+    int64_t bases;           /* sum of w over the participants */
+    int64_t positions;
+    int64_t kmers;           /* the valid positions */
+    int64_t invalid;         /* positions - kmers */
+    /* of the table after the call */
+    int64_t distinct;        /* occupied rows */
+    int64_t singletons;      /* rows with count 1 */
+    int64_t max_count;
+    int64_t max_key;         /* the lowest key among the rows of max_count; -1 for an empty table */
+    int64_t total_count;     /* the sum of all counts */
+    int64_t overflow;        /* inserts given up; 0 on PPG_OK */
+    int64_t reserved[3];
+} ppg_kmer_count_result;
+int ppg_kmer_count_check(const void *kmers);
+int ppg_kmers_count(ppg_ctx *ctx, const void *kmers, const void *set, const uint32_t *dev_mask, int64_t mask_cap,
+                    const void *dev_windows, int64_t windows_cap, void *dev_table, int64_t slots, void *result,
+                    int64_t *spectrum, int64_t spectrum_cap);
+int ppg_kmers_select(ppg_ctx *ctx, const void *dev_table, int64_t slots, int64_t min_count, void *dev_out,
+                     int64_t out_cap, int64_t *found);
+int ppg_kmers_lookup(ppg_ctx *ctx, const void *dev_table, int64_t slots, const void *dev_keys, int64_t nkeys,
+                     int64_t *dev_counts);
+
 /* Library build string (kernel ISA, version). */
 const char *ppg_version(void);
 /* "inflate-<16 hex>": a hash of the inflate kernels' object (all variants + launcher), fixed at

@@ -459,6 +459,19 @@ internal static unsafe class PpGpu
         long* devRec1, long* devRec2, long npairs, void* devRows, long rowCap, long* devSeqOff, uint* devSeqLen,
         long recCap, uint* devBases, uint* devMask, byte* devQual, long baseCap, long* devPairOf, void* result);
 
+    // k-mer counts: the spectrum and the most frequent k-mers of a packed read set (kmers: eight longs -- flags
+    // (1 canonical, 2 use windows, 4 use mask, 8 accumulate), k, six zeros; set: a PpgPackedView*; the mask, windows,
+    // table (slots rows of two ulongs {key, count}, an empty row {~0, 0}), out rows, keys and counts are device
+    // pointers; result: sixteen longs and spectrum: 1024 longs of host memory)
+    [DllImport(Lib)] public static extern int ppg_kmer_count_check(void* kmers);
+    [DllImport(Lib)] public static extern int ppg_kmers_count(nint ctx, void* kmers, void* set, uint* devMask,
+        long maskCap, void* devWindows, long windowsCap, void* devTable, long slots, void* result, long* spectrum,
+        long spectrumCap);
+    [DllImport(Lib)] public static extern int ppg_kmers_select(nint ctx, void* devTable, long slots, long minCount,
+        void* devOut, long outCap, out long found);
+    [DllImport(Lib)] public static extern int ppg_kmers_lookup(nint ctx, void* devTable, long slots, void* devKeys,
+        long nkeys, long* devCounts);
+
     [DllImport(Lib)] public static extern nint ppg_version();
     [DllImport(Lib)] public static extern nint ppg_build_id();
 

@@ -1195,6 +1195,218 @@ def pair_merge(packed1, packed2, rows, merge=None, rec1=None, rec2=None, out=Non
     return PairMergeResult(res, out, None if pair_of is None else pair_of[:int(res.merged)])
 
 
+class KmerCount:
+    """A k-mer count (include/ppgpu.h "k-mer counts"): every k-mer of k bases, 1 <= k <= 31, as the key whose first
+    base is most significant (A 0, C 1, G 2, T 3); canonical: a k-mer and its reverse complement count as one, under
+    the smaller of their keys."""
+
+    _BASES = "ACGT"
+
+    def __init__(self, k=21, canonical=True):
+        self.k, self.canonical = k, bool(canonical)
+
+    def struct(self, use_windows=False, use_mask=False, accumulate=False):
+        """The ppg_kmer_count of this count (with the USE_WINDOWS / USE_MASK / ACCUMULATE bits); ValueError when
+        ppg_kmer_count_check refuses it."""
+        flags = (_lib.PPG_KMER_CANONICAL if self.canonical else 0) | (_lib.PPG_KMER_USE_WINDOWS if use_windows else 0) | \
+            (_lib.PPG_KMER_USE_MASK if use_mask else 0) | (_lib.PPG_KMER_ACCUMULATE if accumulate else 0)
+        c = _lib.PpgKmerCount(flags, int(self.k), (C.c_int64 * 6)())
+        if lib.ppg_kmer_count_check(C.byref(c)) != 0:
+            raise ValueError(f"KmerCount: not a valid k-mer count: {self!r}")
+        return c
+
+    @staticmethod
+    def min_slots(distinct):
+        """The smallest legal table for `distinct` distinct keys: a power of two, at least 64 and 2 x distinct."""
+        return max(64, 1 << max(2 * int(distinct) - 1, 0).bit_length())
+
+    def key(self, word):
+        """The key of a k-mer given as str or bytes of k upper-case ACGT (the canonical key when canonical)."""
+        w = word.decode("ascii") if isinstance(word, (bytes, bytearray)) else str(word)
+        if len(w) != self.k or any(c not in self._BASES for c in w):
+            raise ValueError(f"KmerCount.key: expected {self.k} bases of ACGT, got {word!r}")
+        key = 0
+        for c in w:
+            key = key * 4 + self._BASES.index(c)
+        return self.canonical_key(key) if self.canonical else key
+
+    def canonical_key(self, key):
+        """min(key, the key of the reverse complement)."""
+        key, rc = int(key), 0
+        for i in range(self.k):
+            rc = rc * 4 + (3 - ((key >> (2 * i)) & 3))
+        return min(key, rc)
+
+    def word(self, key):
+        """The k-mer of a key as str (of the canonical key when canonical)."""
+        key = int(key)
+        if not 0 <= key < 4 ** self.k:
+            raise ValueError(f"KmerCount.word: not a key of {self.k} bases: {key}")
+        if self.canonical:
+            key = self.canonical_key(key)
+        return "".join(self._BASES[(key >> (2 * (self.k - 1 - i))) & 3] for i in range(self.k))
+
+    def __repr__(self):
+        return f"KmerCount(k={self.k}, canonical={self.canonical})"
+
+
+class KmerCountResult:
+    """The result of a k-mer count (include/ppgpu.h "k-mer counts"): the totals of the call `records`,
+    `participating`, `short_reads`, `bases`, `positions`, `kmers`, `invalid`; those of the table after it `distinct`,
+    `singletons`, `max_count`, `max_key`, `total_count`; `overflow`; `spectrum` (numpy int64[1024]: rows by count,
+    the last bin >= 1023); `table` (the int64 CUDA tensor [slots, 2] of {key, count} rows, an empty row is -1, 0);
+    `kmers_spec` (the KmerCount) and `retries` (how often a table sized by doubling was too small)."""
+
+    TOTALS = ("records", "participating", "short_reads", "bases", "positions", "kmers", "invalid", "distinct",
+              "singletons", "max_count", "max_key", "total_count", "overflow")
+
+    def __init__(self, result, spectrum, table, kmers_spec, device, retries=0):
+        for name in self.TOTALS:
+            setattr(self, name, int(getattr(result, name)))
+        self.spectrum = np.asarray(spectrum, np.int64)
+        self.table, self.kmers_spec, self.device, self.retries = table, kmers_spec, device, int(retries)
+
+    @property
+    def slots(self):
+        return self.table.numel() // 2
+
+    def select(self, min_count):
+        """numpy uint64 [n, 2]: the {key, count} rows with count >= min_count, in no order (two ppg_kmers_select:
+        one to count, one to fill)."""
+        found = C.c_int64()
+        self.device.after_torch()
+        check(lib.ppg_kmers_select(self.device.handle, C.c_void_p(self.table.data_ptr()), self.slots, int(min_count), None, 0,
+                                   C.byref(found)), "kmers_select")
+        return self._select(int(min_count), found.value)
+
+    def _select(self, min_count, cap):
+        import torch
+        out = torch.empty((max(cap, 1), 2), dtype=torch.int64, device=self.table.device)
+        found = C.c_int64()
+        self.device.after_torch()
+        check(lib.ppg_kmers_select(self.device.handle, C.c_void_p(self.table.data_ptr()), self.slots, min_count,
+                                   C.c_void_p(out.data_ptr()), cap, C.byref(found)), "kmers_select")
+        return out[:found.value].cpu().numpy().view(np.uint64)
+
+    def top(self, n):
+        """[(word, count)] of the n most frequent k-mers (fewer when the table holds fewer), ties by the lower key:
+        the threshold comes from the spectrum, one ppg_kmers_select takes the rows at or above it, the host sorts."""
+        n = min(int(n), self.distinct)
+        if n <= 0:
+            return []
+        above = np.cumsum(self.spectrum[::-1])[::-1]          # above[c]: the rows with count >= c
+        t = max(int(np.nonzero(above >= n)[0][-1]), 1)        # the greatest threshold that still gives n rows
+        rows = self._select(t, int(above[t]))
+        order = np.lexsort((rows[:, 0], -rows[:, 1].astype(np.int64)))[:n]
+        return [(self.kmers_spec.word(int(k)), int(c)) for k, c in rows[order]]
+
+    def lookup(self, words_or_keys):
+        """numpy int64: the count of each k-mer (str / bytes, canonicalised when the count is canonical) or key
+        (int, looked up as given); 0 for one the table does not hold (ppg_kmers_lookup)."""
+        import torch
+        keys = np.array([k if isinstance(k, (int, np.integer)) else self.kmers_spec.key(k) for k in words_or_keys], np.uint64)
+        if keys.size == 0:
+            return np.zeros(0, np.int64)
+        dk = torch.from_numpy(keys.view(np.int64)).to(self.table.device)
+        counts = torch.zeros(keys.size, dtype=torch.int64, device=self.table.device)
+        self.device.after_torch()
+        check(lib.ppg_kmers_lookup(self.device.handle, C.c_void_p(self.table.data_ptr()), self.slots,
+                                   C.c_void_p(dk.data_ptr()), keys.size, C.c_void_p(counts.data_ptr())), "kmers_lookup")
+        return counts.cpu().numpy()
+
+    def __repr__(self):
+        return (f"KmerCountResult(records={self.records}, kmers={self.kmers}, invalid={self.invalid}, "
+                f"distinct={self.distinct}, singletons={self.singletons}, max_count={self.max_count}, slots={self.slots})")
+
+
+def _kmer_slot_range(k, positions):
+    """(first, last) table sizes of a count sized by doubling: the powers of two >= max(64, 2 d / 16) and >= 2 d with
+    d = min(4^k, positions), the most distinct keys there can be; the last cannot fail."""
+    d = min(4 ** int(k), max(int(positions), 0))
+    return KmerCount.min_slots((d + 15) // 16), KmerCount.min_slots(d)
+
+
+def count_kmers_sets(sets, kmers, masks=None, windows=None, table=None, slots=None, accumulate=False, device=None):
+    """count_kmers over several packed read sets into one table: the first as count_kmers would, every further one
+    with ACCUMULATE; masks / windows: one entry (or None) per set.  The KmerCountResult is the last call's: its
+    totals "of the call" are the last set's, those "of the table" are all sets'.  Sized by doubling when neither
+    table nor slots is given: a table that turns out too small starts all sets again in one twice as large."""
+    import torch
+    what = "count_kmers"
+    sets = list(sets)
+    if not sets:
+        raise ValueError(f"{what}: no read set")
+    for p in sets:
+        if not isinstance(p, PackedReads) or not p.on_device:
+            raise ValueError(f"{what}: expected PackedReads of CUDA tensors")
+        p._check_device(what)
+    tdev = sets[0].seq_off.device
+    if any(p.seq_off.device != tdev for p in sets):
+        raise ValueError(f"{what}: the read sets must be on one device")
+    dev = device or Device.default(tdev.index if tdev.index is not None else torch.cuda.current_device())
+    kmers = KmerCount() if kmers is None else kmers
+    if not isinstance(kmers, KmerCount):
+        raise ValueError(f"{what}: expected a KmerCount")
+    masks = list(masks) if masks is not None else [None] * len(sets)
+    windows = list(windows) if windows is not None else [None] * len(sets)
+    if len(masks) != len(sets) or len(windows) != len(sets):
+        raise ValueError(f"{what}: one mask and one windows entry per read set")
+    margs = []
+    for p, m, w in zip(sets, masks, windows):
+        mp, mcap, _ = _mask_arg(m, what)
+        if m is not None and mp is None and p.records:
+            raise ValueError(f"{what}: the mask is empty")
+        if w is not None:
+            _int_tensor_arg(w, (torch.int32, torch.uint32), what, "windows")
+            if w.numel() % 2:
+                raise ValueError(f"{what}: windows must hold two values per record")
+        margs.append((mp, mcap, C.c_void_p(w.data_ptr()) if w is not None else None, w.numel() // 2 if w is not None else 0))
+    if accumulate and table is None:
+        raise ValueError(f"{what}: accumulate needs the table of the earlier count")
+    if table is not None:
+        _int_tensor_arg(table, (torch.int64,), what, "table")
+        if table.device != tdev or table.numel() % 2:
+            raise ValueError(f"{what}: table must hold two int64 per row on the read sets' device")
+        first = last = table.numel() // 2
+    elif slots is not None:
+        first = last = int(slots)
+    else:
+        first, last = _kmer_slot_range(kmers.k, sum(p.total_bases if p.total_bases is not None else p.base_cap for p in sets))
+    views = [_lib.PpgPackedView(p.seq_off.data_ptr(), p.seq_len.data_ptr(), p.bases.data_ptr(), p.mask.data_ptr(),
+                                p.qual.data_ptr() if p.qual is not None else None, p.records) for p in sets]
+    structs = [kmers.struct(use_windows=a[2] is not None, use_mask=a[0] is not None, accumulate=accumulate or i > 0)
+               for i, a in enumerate(margs)]
+    n, retries = first, 0
+    while True:
+        t = table if table is not None else torch.empty((n, 2), dtype=torch.int64, device=tdev)
+        res, spectrum = _lib.PpgKmerCountResult(), np.zeros(_lib.PPG_KMER_SPECTRUM, np.int64)
+        dev.after_torch()
+        rc = 0
+        for v, c, (mp, mcap, wp, wcap) in zip(views, structs, margs):
+            rc = lib.ppg_kmers_count(dev.handle, C.byref(c), C.byref(v), mp, mcap, wp, wcap, C.c_void_p(t.data_ptr()), n,
+                                     C.byref(res), _ptr(spectrum), spectrum.size)
+            if rc != 0:
+                break
+        if rc == _lib.PPG_BUF_ERROR and n < last:
+            del t
+            n, retries = 2 * n, retries + 1
+            continue
+        check(rc, what)
+        return KmerCountResult(res, spectrum, t, kmers, dev, retries)
+
+
+def count_kmers(packed, kmers=None, mask=None, windows=None, table=None, slots=None, accumulate=False, device=None):
+    """The k-mer count `kmers` (a KmerCount, None: k = 21 canonical) of a packed read set on one GPU
+    (ppg_kmers_count), as a KmerCountResult.  packed: a PackedReads of CUDA tensors (qualities not needed).  mask: a
+    SeqQuery with a mask or int32 / uint32 CUDA tensor of hit-mask words by record: only records with their bit set
+    count (None: all).  windows: an int32 / uint32 CUDA tensor of (start, len) rows by record (a trim's): k-mers are
+    taken inside them (None: whole reads).  table: an int64 CUDA tensor [slots, 2] to count into, slots a power of
+    two >= 64; or slots: the size of a new one; or neither: sized by doubling, from a sixteenth of the largest table
+    the input can need, again after every PPG_BUF_ERROR (the result's `retries`).  accumulate: add to what an
+    earlier count with the same KmerCount left in `table`.  Ordered after torch's stream, complete on return."""
+    return count_kmers_sets([packed], kmers, [mask], [windows], table, slots, accumulate, device)
+
+
 class SelectedRecords:
     """The records a mask selects (include/ppgpu.h "record selection"): `bytes` (uint8, the selected
     records' text back to back), `sel_off` (int64, records + 1 offsets into it), `desc` (records x 4:
@@ -2386,6 +2598,30 @@ class BatchedFASTQ:
             mask, rows = self._chain(sh, nrec, pattern, filter, trim, dedup)
             return sh.set_readprofile(profile, mask=mask, windows=rows).run().readprofile
         finally:
+            self._stage_shard()
+
+    def CountKmers(self, kmers=None, pattern=None, filter=None, trim=None, dedup=None, slots=None):   # noqa: A002
+        """The KmerCountResult of the file: the k-mer spectrum, the totals and the table of every k-mer's count
+        (kmers: a KmerCount, None for k = 21 canonical), counted on the GPU (count_kmers).  The reads are packed
+        without qualities while each batch is resident (Shard.set_seqpack), so a file of any number of batches leaves
+        its whole packed set on the device; with pattern / filter / trim / dedup the same run chains their hooks onto
+        one mask and one rows tensor as Profile does, and the k-mers are those of the reads that contain the pattern,
+        pass the filter, are kept by the trim and (dedup) are first occurrences, inside the trim's windows.  A record
+        the reference parses twice counts twice, as in the profile; with dedup the second is dropped.  slots: the
+        table's size (None: sized by doubling)."""
+        sh = self._stage_shard()
+        nrec = self._stage_records(sh)
+        tot, rec = sh.seq_bases()
+        packed = PackedReads.empty(rec, tot, False, sh.dev.device)
+        try:
+            sh.set_seqpack(packed)
+            mask, rows = self._chain(sh, nrec, pattern, filter, trim, dedup)
+            sh.run()
+            if not sh.seqpack_ready:
+                raise ValueError("CountKmers: the shard's run did not fill the packed reads")
+            return count_kmers(packed, kmers, mask=mask, windows=rows, slots=slots, device=sh.dev)
+        finally:
+            sh.set_seqpack(None)
             self._stage_shard()
 
     def QualityCounts(self):

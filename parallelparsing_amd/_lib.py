@@ -182,6 +182,10 @@ _SIGS = {
     "ppg_pair_merge_check": (C.c_int, [vp]),
     "ppg_pairs_merge_size": (C.c_int, [vp, vp, vp, vp, vp, i64, vp, i64, P(i64), P(i64)]),
     "ppg_pairs_merge": (C.c_int, [vp, vp, vp, vp, vp, vp, i64, vp, i64, vp, vp, i64, vp, vp, vp, i64, vp, vp]),
+    "ppg_kmer_count_check": (C.c_int, [vp]),
+    "ppg_kmers_count": (C.c_int, [vp, vp, vp, vp, i64, vp, i64, vp, i64, vp, vp, i64]),
+    "ppg_kmers_select": (C.c_int, [vp, vp, i64, i64, vp, i64, P(i64)]),
+    "ppg_kmers_lookup": (C.c_int, [vp, vp, i64, vp, i64, vp]),
 }
 
 
@@ -299,6 +303,22 @@ class PpgPairMergeResult(C.Structure):
                 ("stale", C.c_int64), ("merged", C.c_int64), ("merged_bases", C.c_int64), ("padded_bases", C.c_int64),
                 ("overlap_bases", C.c_int64), ("disagree", C.c_int64), ("from2", C.c_int64), ("ties", C.c_int64),
                 ("n_filled", C.c_int64), ("n_both", C.c_int64), ("corrected", C.c_int64 * 2)]
+
+
+class PpgKmerCount(C.Structure):
+    """ppg_kmer_count (include/ppgpu.h)."""
+    _fields_ = [("flags", C.c_int64), ("k", C.c_int64), ("reserved", C.c_int64 * 6)]
+
+
+class PpgKmerCountResult(C.Structure):
+    """ppg_kmer_count_result (include/ppgpu.h)."""
+    _fields_ = [("records", C.c_int64), ("participating", C.c_int64), ("short_reads", C.c_int64), ("bases", C.c_int64),
+                ("positions", C.c_int64), ("kmers", C.c_int64), ("invalid", C.c_int64), ("distinct", C.c_int64),
+                ("singletons", C.c_int64), ("max_count", C.c_int64), ("max_key", C.c_int64), ("total_count", C.c_int64),
+                ("overflow", C.c_int64), ("reserved", C.c_int64 * 3)]
+
+
+PPG_KMER_CANONICAL, PPG_KMER_USE_WINDOWS, PPG_KMER_USE_MASK, PPG_KMER_ACCUMULATE, PPG_KMER_SPECTRUM = 1, 2, 4, 8, 1024
 
 
 for _name, (_res, _args) in _SIGS.items():

@@ -184,6 +184,15 @@ struct alignas(16) PpgMergeRec {
     uint32_t pad;
 };
 
+// a ppg_kmer_count (include/ppgpu.h "k-mer counts") as the k-mer kernels' argument
+struct PpgKmerCount {
+    int64_t flags, k, reserved[6];
+};
+// the k-mer counter's accumulators: the int64 fields of a ppg_kmer_count_result in order (records, participating,
+// short_reads, bases, positions, kmers, invalid, distinct, singletons, max_count, max_key, total_count, overflow,
+// reserved[3]), then the claimed-rows counter and the select's cursor, and from kKmSpecAt on the spectrum's kKmSpectrum bins
+constexpr int kKmAcc = 16, kKmClaimed = 16, kKmCursor = 17, kKmSpecAt = 32, kKmSpectrum = 1024, kKmAccAll = kKmSpecAt + kKmSpectrum;
+
 // ppg_sel_copy: the destination bytes one workgroup writes (256 threads x 4 words of 16 B); ppg_sel_place
 // records, per multiple of it inside a batch's destination range, the selected record that holds that byte
 constexpr uint32_t kSelSpan = 16384;

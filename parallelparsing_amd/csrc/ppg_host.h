@@ -116,6 +116,7 @@ struct ppg_ctx {
     size_t stage_n = 0;
     int overlap_grid = 0;               // ppg_po_overlap's grid (0: the default; the tests force small ones)
     int merge_grid = 0;                 // ppg_pm_emit's grid, likewise
+    int kmer_grid = 0;                  // ppg_km_insert's grid, likewise
 };
 
 template <class T>

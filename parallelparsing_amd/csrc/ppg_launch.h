@@ -161,6 +161,24 @@ PPG_WEAK hipError_t ppg_launch_pm_emit(hipStream_t s, const PpgPackedView &s1, c
                                        int64_t padded_bases, const PpgPairMerge *pm, uint32_t *bases, uint32_t *mask,
                                        uint8_t *qual, uint64_t *acc, int blocks, int cus);
 
+// ---- ppg_kmercount.hip ----
+// Weak for the same reason (kmercount_linked, ppg_stages.cpp).  One packed read set; words / rows: the record
+// mask and the windows or null; umap: a record number per 32-base unit; table: slots rows of {key, count};
+// acc: kKmAccAll values.
+PPG_WEAK hipError_t ppg_launch_km_init(hipStream_t s, uint64_t *table, uint64_t slots, int accumulate, uint64_t *acc);
+PPG_WEAK hipError_t ppg_launch_km_records(hipStream_t s, const PpgPackedView &set, const uint32_t *words,
+                                          const uint32_t *rows, const PpgKmerCount *kc, uint64_t units, uint32_t *umap,
+                                          uint64_t *acc);
+PPG_WEAK hipError_t ppg_launch_km_insert(hipStream_t s, const PpgPackedView &set, const uint32_t *words,
+                                         const uint32_t *rows, const uint32_t *umap, const PpgKmerCount *kc,
+                                         uint64_t units, uint64_t *table, uint64_t slots, uint64_t *acc, int blocks,
+                                         int cus);
+PPG_WEAK hipError_t ppg_launch_km_stats(hipStream_t s, const uint64_t *table, uint64_t slots, uint64_t *acc);
+PPG_WEAK hipError_t ppg_launch_km_select(hipStream_t s, const uint64_t *table, uint64_t slots, int64_t min_count,
+                                         uint64_t *out, int64_t out_cap, uint64_t *cursor);
+PPG_WEAK hipError_t ppg_launch_km_lookup(hipStream_t s, const uint64_t *table, uint64_t slots, const uint64_t *keys,
+                                         int64_t nkeys, int64_t *counts);
+
 // ---- ppg_seqselect.hip ----
 // Weak for the same reason (select_linked, ppg_stages.cpp).
 PPG_WEAK hipError_t ppg_launch_sel_count(hipStream_t s, const PpgBatchView &v, const uint32_t *mask, uint64_t bit0,

@@ -45,23 +45,15 @@
 #include <algorithm>
 #include "ppg_device.h"
 #include "ppg_launch.h"
+#include "ppg_mix.h"
 #include "ppg_seqload.h"
 
 namespace {
 
-constexpr unsigned long long kDdMul = 0xD6E8FEB86659FD93ull, kDdGold = 0x9E3779B97F4A7C15ull,
-                             kDdLen = 0x632BE59BD9B4E019ull;
+// (dd_mix: ppg_mix.h)
+constexpr unsigned long long kDdGold = 0x9E3779B97F4A7C15ull, kDdLen = 0x632BE59BD9B4E019ull;
 // the record's second scratch word when it has no row: it does not participate / its probe found none
 constexpr unsigned long long kDdNone = ~0ull, kDdOver = ~0ull - 1;
-
-__device__ __forceinline__ unsigned long long dd_mix(unsigned long long x) {
-    x ^= x >> 32;
-    x *= kDdMul;
-    x ^= x >> 32;
-    x *= kDdMul;
-    x ^= x >> 32;
-    return x;
-}
 
 // the window (s, w) of a record of Sequence length L (row r of `rows` clamped, or (0, L)) and from it the
 // key bytes' start and length

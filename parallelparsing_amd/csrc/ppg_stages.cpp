@@ -5,7 +5,8 @@
 // pieces on one batch, its C entry points (one-shot on a one-batch shard, the hook of every batch of a
 // run, and what the last run left) and the measurement hook of its tools/*_probe.py.  The pair overlap
 // (ppg_pairoverlap.hip) is here as well: it has no batch, it reads two packed read sets the pack stage wrote; so is
-// the pair merge (ppg_pairmerge.hip), which makes a third packed read set from those two and the overlap's rows.
+// the pair merge (ppg_pairmerge.hip), which makes a third packed read set from those two and the overlap's rows, and
+// the k-mer counter (ppg_kmercount.hip), which counts one packed read set's k-mers into a table of the caller's.
 //
 // A batch's hooks run from one place, shard_batch_hooks, called once by batch_collect (ppg_api.cpp).  The
 // unit kernels of query, filter, trim, dedup and profile read one layout of the batch (StageLayout, ppg_host.h), which
@@ -29,7 +30,9 @@ static_assert(sizeof(ppg_seq_query_result) == 8 * 8 && sizeof(ppg_read_filter_re
                   sizeof(ppg_pair_overlap_result) == 8 * kPoAcc && sizeof(ppg_pair_overlap) == sizeof(PpgPairOverlap) &&
                   sizeof(ppg_packed_view) == sizeof(PpgPackedView) && PPG_OVERLAP_MAX_LEN == kPoMaxLen &&
                   PPG_OVERLAP_HIST == kPoHist && sizeof(ppg_pair_merge_result) == 8 * kPmAcc &&
-                  sizeof(ppg_pair_merge) == sizeof(PpgPairMerge) && sizeof(ppg_pair_merge) == 64 && sizeof(PpgMergeRec) == 32,
+                  sizeof(ppg_pair_merge) == sizeof(PpgPairMerge) && sizeof(ppg_pair_merge) == 64 && sizeof(PpgMergeRec) == 32 &&
+                  sizeof(ppg_kmer_count_result) == 8 * kKmAcc && sizeof(ppg_kmer_count) == sizeof(PpgKmerCount) &&
+                  sizeof(ppg_kmer_count) == 64 && PPG_KMER_SPECTRUM == kKmSpectrum,
               "a stage's result struct is its accumulators");
 
 static bool seq_linked() {   // (weak references, ppg_launch.h: absent from the host-only sanitizer build)
@@ -491,6 +494,74 @@ struct PairMergeScratch {
     uint64_t *rbase(int n) { return tiles.p + 2 * ((size_t)n + 1); }
     uint64_t *bbase(int n) { return tiles.p + 3 * ((size_t)n + 1); }
 };
+
+// ---- k-mer counts (ppg_kmercount.hip) ----
+// As the overlap: one packed read set in caller memory, on the ctx stream; the table is the caller's too.
+static bool kmercount_linked() {
+    return ppg_launch_km_init && ppg_launch_km_records && ppg_launch_km_insert && ppg_launch_km_stats &&
+           ppg_launch_km_select && ppg_launch_km_lookup;
+}
+
+// the rules of include/ppgpu.h "k-mer counts"; host only
+static bool kmercount_ok(const void *kmers, PpgKmerCount *out) {
+    if (!kmers) return false;
+    PpgKmerCount c;
+    memcpy(&c, kmers, sizeof c);
+    if ((c.flags & ~(int64_t)(PPG_KMER_CANONICAL | PPG_KMER_USE_WINDOWS | PPG_KMER_USE_MASK | PPG_KMER_ACCUMULATE)) != 0 ||
+        c.k < 1 || c.k > 31)
+        return false;
+    for (int64_t r : c.reserved)
+        if (r != 0) return false;
+    if (out) *out = c;
+    return true;
+}
+
+static bool kmer_table_ok(const void *table, int64_t slots) {
+    return table && ((uintptr_t)table & 15) == 0 && slots >= 64 && (slots & (slots - 1)) == 0;
+}
+
+struct KmerCountArgs {
+    PpgKmerCount kc;
+    PpgPackedView set;
+};
+
+// PPG_ARG_ERROR / PPG_BUF_ERROR of ppg_kmers_count, before anything is written
+static int kmercount_args(ppg_ctx *ctx, const void *kmers, const void *set, const uint32_t *mask, int64_t mask_cap,
+                          const void *windows, int64_t windows_cap, const void *table, int64_t slots, const int64_t *spectrum,
+                          int64_t spectrum_cap, KmerCountArgs &a) {
+    if (!ctx || !kmercount_ok(kmers, &a.kc) || !packed_view_ok(set, &a.set)) return PPG_ARG_ERROR;
+    if (mask_cap < 0 || mask_cap % 32 != 0 || windows_cap < 0 || spectrum_cap < 0 || !kmer_table_ok(table, slots)) return PPG_ARG_ERROR;
+    if (((uintptr_t)mask & 3) || ((uintptr_t)windows & 7) || a.set.records >= (int64_t)0xFFFFFFFFu) return PPG_ARG_ERROR;
+    // a flag without its buffer, a buffer without its flag
+    if (((a.kc.flags & PPG_KMER_USE_MASK) != 0) != (mask != nullptr) || ((a.kc.flags & PPG_KMER_USE_WINDOWS) != 0) != (windows != nullptr))
+        return PPG_ARG_ERROR;
+    if ((mask && a.set.records > mask_cap) || (windows && a.set.records > windows_cap) || (spectrum && spectrum_cap < kKmSpectrum))
+        return PPG_BUF_ERROR;
+    return PPG_OK;
+}
+
+// the call's scratch: the accumulators and the record of every 32-base unit
+struct KmerCountScratch {
+    DevBuf<uint64_t> acc;
+    DevBuf<uint32_t> umap;
+    uint64_t units = 0;
+};
+
+// the set's 32-base units, from seq_off[records] (one 8-byte copy; blocks)
+static int kmercount_units(hipStream_t s, const PpgPackedView &set, uint64_t *units) {
+    int64_t total = 0;
+    HIPCHK(hipMemcpyAsync(&total, set.seq_off + set.records, 8, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    if (total < 0 || total % 32 != 0) return PPG_ARG_ERROR;   // not a packed read set
+    *units = (uint64_t)total / 32;
+    return PPG_OK;
+}
+
+// the accumulators as a pass over the table wants them: all zero, max_key all ones
+static hipError_t kmercount_clear(hipStream_t s, uint64_t *acc, bool all) {
+    hipError_t e = all ? hipMemsetAsync(acc, 0, 8 * (size_t)kKmAccAll, s) : hipSuccess;
+    return e != hipSuccess ? e : hipMemsetAsync(acc + 10, 0xFF, 8, s);
+}
 
 // count and scan, queued on s; the totals are in w.host once s has been synchronised
 static int pairmerge_count(hipStream_t s, const PairMergeArgs &a, const int64_t *rec1, const int64_t *rec2, int64_t npairs,
@@ -1086,6 +1157,83 @@ int ppg_pairs_merge(ppg_ctx *ctx, const void *merge, const void *set1, const voi
     return PPG_OK;
 }
 
+// ---- k-mer counts: blocking calls on the ctx stream ----
+int ppg_kmer_count_check(const void *kmers) { return kmercount_ok(kmers, nullptr) ? PPG_OK : PPG_ARG_ERROR; }
+
+// the empty table (or the count of its rows), the unit table with the call's totals, and the insert, queued on s
+static int kmercount_insert(ppg_ctx *ctx, hipStream_t s, const KmerCountArgs &a, const uint32_t *mask, const void *windows,
+                            void *table, int64_t slots, KmerCountScratch &w, int cus) {
+    HIPCHK(ppg_launch_km_init(s, (uint64_t *)table, (uint64_t)slots, (a.kc.flags & PPG_KMER_ACCUMULATE) != 0, w.acc.p));
+    if (w.units) HIPCHK(hipMemsetAsync(w.umap.p, 0xFF, 4 * (size_t)w.units, s));
+    HIPCHK(ppg_launch_km_records(s, a.set, mask, (const uint32_t *)windows, &a.kc, w.units, w.umap.p, w.acc.p));
+    HIPCHK(ppg_launch_km_insert(s, a.set, mask, (const uint32_t *)windows, w.umap.p, &a.kc, w.units, (uint64_t *)table,
+                                (uint64_t)slots, w.acc.p, ctx->kmer_grid, cus));
+    return PPG_OK;
+}
+
+int ppg_kmers_count(ppg_ctx *ctx, const void *kmers, const void *set, const uint32_t *dev_mask, int64_t mask_cap,
+                    const void *dev_windows, int64_t windows_cap, void *dev_table, int64_t slots, void *result,
+                    int64_t *spectrum, int64_t spectrum_cap) {
+    KmerCountArgs a;
+    if (int rc = kmercount_args(ctx, kmers, set, dev_mask, mask_cap, dev_windows, windows_cap, dev_table, slots, spectrum,
+                                spectrum_cap, a))
+        return rc;
+    if (!kmercount_linked()) return PPG_UNSUPPORTED;
+    HIPCHK(hipSetDevice(ctx->device));
+    hipStream_t s = ctx->stream;
+    int cus = 0;
+    HIPCHK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, ctx->device));
+    KmerCountScratch w;
+    if (int rc = kmercount_units(s, a.set, &w.units)) return rc;
+    HIPCHK(w.acc.alloc(kKmAccAll));
+    HIPCHK(w.umap.alloc((size_t)w.units));
+    HIPCHK(kmercount_clear(s, w.acc.p, true));
+    if (int rc = kmercount_insert(ctx, s, a, dev_mask, dev_windows, dev_table, slots, w, cus)) return rc;
+    HIPCHK(ppg_launch_km_stats(s, (const uint64_t *)dev_table, (uint64_t)slots, w.acc.p));
+    std::vector<int64_t> h((size_t)kKmAccAll);
+    HIPCHK(hipMemcpyAsync(h.data(), w.acc.p, 8 * h.size(), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    if (h[12] != 0 || h[7] > slots / 2) return PPG_BUF_ERROR;   // the table's contents are unspecified; nothing else is written
+    h[6] = h[4] - h[5];
+    if (h[9] == 0) h[10] = -1;   // an empty table
+    if (result) memcpy(result, h.data(), sizeof(ppg_kmer_count_result));
+    if (spectrum) memcpy(spectrum, h.data() + kKmSpecAt, 8 * (size_t)kKmSpectrum);
+    return PPG_OK;
+}
+
+int ppg_kmers_select(ppg_ctx *ctx, const void *dev_table, int64_t slots, int64_t min_count, void *dev_out, int64_t out_cap,
+                     int64_t *found) {
+    if (!ctx || !kmer_table_ok(dev_table, slots) || min_count < 1 || out_cap < 0 || ((uintptr_t)dev_out & 15) ||
+        (!dev_out && out_cap > 0))
+        return PPG_ARG_ERROR;
+    if (!kmercount_linked()) return PPG_UNSUPPORTED;
+    HIPCHK(hipSetDevice(ctx->device));
+    hipStream_t s = ctx->stream;
+    DevBuf<uint64_t> cursor;
+    HIPCHK(cursor.alloc(1));
+    HIPCHK(hipMemsetAsync(cursor.p, 0, 8, s));
+    HIPCHK(ppg_launch_km_select(s, (const uint64_t *)dev_table, (uint64_t)slots, min_count, (uint64_t *)dev_out,
+                                dev_out ? out_cap : 0, cursor.p));
+    int64_t n = 0;
+    HIPCHK(hipMemcpyAsync(&n, cursor.p, 8, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    if (found) *found = n;
+    return dev_out && n > out_cap ? PPG_BUF_ERROR : PPG_OK;   // (without dev_out the call only counts)
+}
+
+int ppg_kmers_lookup(ppg_ctx *ctx, const void *dev_table, int64_t slots, const void *dev_keys, int64_t nkeys,
+                     int64_t *dev_counts) {
+    if (!ctx || !kmer_table_ok(dev_table, slots) || nkeys < 0 || ((uintptr_t)dev_keys & 7) || ((uintptr_t)dev_counts & 7) ||
+        ((!dev_keys || !dev_counts) && nkeys > 0))
+        return PPG_ARG_ERROR;
+    if (!kmercount_linked()) return PPG_UNSUPPORTED;
+    HIPCHK(hipSetDevice(ctx->device));
+    HIPCHK(ppg_launch_km_lookup(ctx->stream, (const uint64_t *)dev_table, (uint64_t)slots, (const uint64_t *)dev_keys, nkeys,
+                                dev_counts));
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    return PPG_OK;
+}
+
 // ---- record selection: the sequence queries entry points' counterparts ----
 static bool select_bufs_ok(const int64_t *recno, const int64_t *sel_off, const uint32_t *desc, int64_t sel_cap,
                            const uint8_t *bytes, int64_t byte_cap) {
@@ -1557,6 +1705,95 @@ int ppgx_pairmerge_times(ppg_ctx *ctx, const void *merge, const void *set1, cons
 int ppgx_pairmerge_grid(ppg_ctx *ctx, int blocks) {
     if (!ctx || blocks < 0) return PPG_ARG_ERROR;
     ctx->merge_grid = blocks;
+    return PPG_OK;
+}
+
+// tools/kmercount_probe.py.  The set without mask and windows into the caller's table (emptied every time; the
+// ACCUMULATE bit is refused).  ms[0]: the table made empty; ms[1]: the unit table and the call's totals; ms[2]: the
+// insert, with the emptying before it taken off (so it is the median of a difference); ms[3]: the spectrum's two
+// passes; ms[4]: a select of every row with count >= 2 into scratch of the hook's own; ms[5]: a lookup of those rows'
+// keys.  sizes[0..3]: valid k-mers, distinct keys, the selected rows, the overflow count of the last insert (not
+// 0: the table is undersized, and the passes after the insert saw an unspecified table).  The stream is the ctx's.
+int ppgx_kmercount_times(ppg_ctx *ctx, const void *kmers, const void *set, void *dev_table, int64_t slots, int reps,
+                         float *ms, int64_t *sizes) {
+    KmerCountArgs a;
+    if (!ms || !sizes || reps < 1) return PPG_ARG_ERROR;
+    if (int rc = kmercount_args(ctx, kmers, set, nullptr, 0, nullptr, 0, dev_table, slots, nullptr, 0, a)) return rc;
+    if (a.kc.flags & PPG_KMER_ACCUMULATE) return PPG_ARG_ERROR;
+    if (!kmercount_linked()) return PPG_UNSUPPORTED;
+    HIPCHK(hipSetDevice(ctx->device));
+    hipStream_t s = ctx->stream;
+    int cus = 0;
+    HIPCHK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, ctx->device));
+    KmerCountScratch w;
+    if (int rc = kmercount_units(s, a.set, &w.units)) return rc;
+    DevBuf<uint64_t> out, keys;
+    DevBuf<int64_t> counts;
+    const int64_t cap = slots / 2;
+    HIPCHK(w.acc.alloc(kKmAccAll));
+    HIPCHK(w.umap.alloc((size_t)w.units));
+    HIPCHK(out.alloc(2 * (size_t)cap));
+    HIPCHK(keys.alloc((size_t)cap));
+    HIPCHK(counts.alloc((size_t)cap));
+    uint64_t *table = (uint64_t *)dev_table;
+    int64_t nsel = 0;
+    float t[7];
+    const int rc = time_steps(s, 7, reps, t, [&](int step) {
+        hipError_t e = hipSuccess;
+        switch (step) {
+            case 0: return ppg_launch_km_init(s, table, (uint64_t)slots, 0, w.acc.p);
+            case 1:
+                e = kmercount_clear(s, w.acc.p, true);
+                if (e == hipSuccess && w.units) e = hipMemsetAsync(w.umap.p, 0xFF, 4 * (size_t)w.units, s);
+                return e != hipSuccess ? e : ppg_launch_km_records(s, a.set, nullptr, nullptr, &a.kc, w.units, w.umap.p, w.acc.p);
+            case 2:
+                e = kmercount_clear(s, w.acc.p, true);
+                if (e == hipSuccess) e = ppg_launch_km_init(s, table, (uint64_t)slots, 0, w.acc.p);
+                return e != hipSuccess ? e
+                                       : ppg_launch_km_insert(s, a.set, nullptr, nullptr, w.umap.p, &a.kc, w.units, table,
+                                                              (uint64_t)slots, w.acc.p, ctx->kmer_grid, cus);
+            case 3: {
+                // (the insert's totals stay: only the passes' own accumulators are cleared)
+                e = hipMemsetAsync(w.acc.p + 7, 0, 8 * 5, s);
+                if (e == hipSuccess) e = hipMemsetAsync(w.acc.p + kKmSpecAt, 0, 8 * (size_t)kKmSpectrum, s);
+                if (e == hipSuccess) e = kmercount_clear(s, w.acc.p, false);
+                return e != hipSuccess ? e : ppg_launch_km_stats(s, table, (uint64_t)slots, w.acc.p);
+            }
+            case 4:
+                e = hipMemsetAsync(w.acc.p + kKmCursor, 0, 8, s);
+                return e != hipSuccess ? e : ppg_launch_km_select(s, table, (uint64_t)slots, 2, out.p, cap, w.acc.p + kKmCursor);
+            case 5: {
+                // the selected rows' keys, once
+                e = hipMemcpyAsync(&nsel, w.acc.p + kKmCursor, 8, hipMemcpyDeviceToHost, s);
+                if (e == hipSuccess) e = hipStreamSynchronize(s);
+                nsel = std::min(nsel, cap);
+                if (e == hipSuccess && nsel)
+                    e = hipMemcpy2DAsync(keys.p, 8, out.p, 16, 8, (size_t)nsel, hipMemcpyDeviceToDevice, s);
+                return e;
+            }
+            default: return ppg_launch_km_lookup(s, table, (uint64_t)slots, keys.p, nsel, counts.p);
+        }
+    });
+    if (rc) return rc;
+    ms[0] = t[0];
+    ms[1] = t[1];
+    ms[2] = t[2] - t[0];
+    ms[3] = t[3];
+    ms[4] = t[4];
+    ms[5] = t[6];
+    int64_t h[kKmAcc];
+    HIPCHK(hipMemcpy(h, w.acc.p, sizeof h, hipMemcpyDeviceToHost));
+    sizes[0] = h[5];
+    sizes[1] = h[7];
+    sizes[2] = nsel;
+    sizes[3] = h[12];
+    return PPG_OK;
+}
+
+// ppg_km_insert's grid on this ctx from now on (0: the default).  The tests force one block and uneven shares with it.
+int ppgx_kmercount_grid(ppg_ctx *ctx, int blocks) {
+    if (!ctx || blocks < 0) return PPG_ARG_ERROR;
+    ctx->kmer_grid = blocks;
     return PPG_OK;
 }
 

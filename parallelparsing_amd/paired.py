@@ -17,7 +17,8 @@ import ctypes as C
 
 import numpy as np
 
-from . import Device, IndexIO, PackedReads, PairOverlap, Shard, pair_merge, pair_overlap, records_from_descriptors
+from . import (Device, IndexIO, PackedReads, PairOverlap, Shard, count_kmers_sets, pair_merge, pair_overlap,
+               records_from_descriptors)
 from ._lib import lib, check, PpgPairResult
 
 DUP = -2      # key of a record parsed twice (Q1), dropped before pairing
@@ -248,6 +249,15 @@ class PairedFASTQ:
         r = pair_merge(packed[0], packed[1], ov.rows, merge, maps[0], maps[1], device=self.dev)
         r.overlap = ov
         return r
+
+    def CountKmers(self, kmers=None, slots=None):
+        """The k-mer count (include/ppgpu.h "k-mer counts") of both files in one table, as a KmerCountResult: R1 is
+        counted, then R2 with ACCUMULATE, so the table, the spectrum and the totals "of the table" are those of all
+        reads of the pair of files (the totals "of the call" are R2's).  Both files are packed without qualities on
+        the device; every record of both shards counts, a record parsed twice as well.  kmers: a KmerCount (None:
+        k = 21 canonical); slots: the table's size (None: sized by doubling)."""
+        packed = [self._packed(f) for f in (0, 1)]
+        return count_kmers_sets(packed, kmers, slots=slots, device=self.dev)
 
     def pair_chunks(self):
         """Yield (j, R1 records, R2 records) for every pair chunk in order."""
